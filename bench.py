@@ -18,6 +18,14 @@ reported alongside.
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1
 it is launched under torch.distributed.run with one rank per GPU over RCCL.
 Rank 0 prints exactly one JSON line.
+
+A plain run reaches the serving steady state without paying for it: the
+conversation ensemble is advanced on the host to where the drained guard
+would leave it and the users' histories are registered in the prefix cache
+(see seed_steady_state), so only the warmup and the timed steps run on the
+GPU. `--full` reaches the same state the long way, by really prefilling
+every history and mixing for 400 steps, as every run did before the option
+existed. `--dump-outputs DIR` writes what the last timed step returned.
 """
 
 import argparse
@@ -68,6 +76,8 @@ class User:
         self.num_rounds = num_rounds
         self.round = 0
         self.submit_time = 0.0
+        # answer tokens still owed for a round fast_forward() stopped in
+        self.pending = None
         # randomized FIRST answer length desynchronizes the user rounds
         self.first_len = int(rng.integers(10, 2 * ANSWER_TOKENS))
         self._new_conversation()
@@ -93,9 +103,15 @@ class User:
         ).tolist()
 
     def answer_len(self) -> int:
+        if self.pending is not None:
+            return self.pending
         return self.first_len if self.round <= 1 else ANSWER_TOKENS
 
     def next_prompt(self) -> list:
+        if self.pending is not None:
+            # mid-answer after fast_forward(): the history already ends
+            # with the question and the part of the answer given so far
+            return list(self.history)
         if self.round >= getattr(self, "rounds_this_conv",
                                  self.num_rounds):
             self._new_conversation()
@@ -108,6 +124,66 @@ class User:
 
     def complete(self, answer_tokens: list) -> None:
         self.history.extend(answer_tokens)
+        self.pending = None
+
+    def fast_forward(self, steps: float) -> None:
+        """Live through `steps` engine steps on the host alone: a round
+        costs one step for its prompt and one per answer token, and its
+        answer is random ids (what a random-weight model gives anyway).
+        Stops inside a round, with `pending` answer tokens still to
+        generate, so users come out at uniformly spread decode phases."""
+        while True:
+            self.next_prompt()
+            want = self.answer_len()
+            given = int(steps) - 1
+            if given < want:
+                break
+            self.complete(self.rng.integers(
+                VOCAB_LOW, self.vocab_high, size=want).tolist())
+            steps -= want + 1
+        given = max(given, 0)
+        self.history.extend(self.rng.integers(
+            VOCAB_LOW, self.vocab_high, size=given).tolist())
+        self.pending = want - given
+
+
+def seed_steady_state(engine, users, budget: int, mixing_steps: int) -> None:
+    """Put `users` and the engine's prefix cache where the drained guard
+    (--full) leaves them, without running the model.
+
+    The guard prefills every user's history in admission order at `budget`
+    tokens a step, waits for 20 steps of equilibrium and mixes for
+    `mixing_steps` more; a user whose prompt drained at step t has by then
+    lived horizon - t steps of its conversation stream. Each user is
+    advanced by exactly that on the host. Then the full blocks of every
+    history are entered into the prefix cache as already computed, so the
+    first prompts only compute their last partial block. The KV those
+    blocks hold is the cache's zero fill: attention reads and multiplies it
+    all the same, and a step's cost does not depend on the values."""
+    fresh = [len(u.history) - len(u.system) + QUESTION_TOKENS
+             for u in users]
+    horizon = sum(fresh) / budget + 20 + mixing_steps
+    t = 0.0
+    for u, n in zip(users, fresh):
+        t += n / budget
+        u.fast_forward(horizon - t)
+    bm = engine.block_manager
+    if not bm.enable_prefix_caching:
+        return
+    bs = bm.block_size
+    for u in users:
+        prev = None
+        for i in range(len(u.history) // bs):
+            h = bm.chain_hash(prev, tuple(u.history[i * bs:(i + 1) * bs]))
+            prev = h
+            if h in bm.cached:
+                continue
+            if not bm.free:
+                return  # cache full: the rest prefills for real
+            blk = bm.free.popleft()
+            bm.cached[h] = blk
+            bm.block_hash[blk] = h
+            bm.evictable[blk] = None
 
 
 def main() -> None:
@@ -131,6 +207,13 @@ def main() -> None:
                     action="store_false", default=True,
                     help="restore the split graph+eager mixed-step path "
                          "(unified reads weights once per step; default)")
+    ap.add_argument("--full", action="store_true",
+                    help="reach the steady state by really prefilling every "
+                         "user's history and mixing for 400 steps (minutes "
+                         "of GPU time) instead of seeding it on the host")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -195,6 +278,7 @@ def main() -> None:
     in_window = False
     in_steady = False
     window_tokens = 0
+    last_outputs: list = []
     done_once: set = set()
 
     def submit(user: User) -> None:
@@ -209,12 +293,15 @@ def main() -> None:
                            ignore_eos=True),
         )
 
-    for u in users:
-        submit(u)
-
     def run_step() -> None:
-        nonlocal window_tokens
-        for out in engine.step():
+        nonlocal window_tokens, last_outputs
+        outs = engine.step()
+        if in_window and args.dump_outputs:
+            last_outputs = [
+                (answers[o.request_id][0], o) for o in outs
+                if o.request_id in answers
+            ]
+        for out in outs:
             entry = answers.get(out.request_id)
             if entry is None:
                 continue
@@ -233,41 +320,56 @@ def main() -> None:
                 done_once.add(user.uid)
                 submit(user)
 
-    # Steady-state guard: the timed window must measure the serving steady
-    # state no matter what --steps/--warmup the driver passes.  The initial
-    # prefill wave of `users` x ~1.1k-token prompts needs
-    # ~users*1100/max_num_batched_tokens steps to drain, far more than a
-    # typical --warmup.  So before honoring --warmup we keep stepping until
-    # >=90% of users have completed their first round (mixed
-    # prefill-over-decode steady state), with a hard time cap as a
-    # safety net.  Only then do the driver's warmup steps run.
-    steady_target = max(1, int(0.9 * len(users)))
-    t_guard = time.perf_counter()
-    guard_cap_s = 300.0 if use_cuda else 120.0
-    guard_steps = 0
-    max_wait = max(2, int(0.05 * len(users)))
-    stable = 0
-    while True:
-        if time.perf_counter() - t_guard >= guard_cap_s:
-            break
-        ok = (len(done_once) >= steady_target
-              and engine.scheduler.num_waiting <= max_wait)
-        stable = stable + 1 if ok else 0
-        if stable >= 20:  # equilibrium must HOLD, not just flicker
-            break
-        run_step()
-        guard_steps += 1
-    # the drain criterion exits before the ensemble's age structure is
-    # stationary: conversation resets (the expensive 3.6k-token
-    # prefills) only ramp in over ~1 conversation period (~1000 steps),
-    # so a 20-step window right after the drain read ~30% above what
-    # 60-200-step windows agree on. A fixed mixing period lets short
-    # driver windows read the converged value
-    for _ in range(400 if use_cuda else 5):
-        if time.perf_counter() - t_guard >= guard_cap_s:
-            break
-        run_step()
-        guard_steps += 1
+    mixing_steps = 400 if use_cuda else 5
+    if not args.full:
+        seed_steady_state(engine, users, args.max_num_batched_tokens,
+                          mixing_steps)
+    for u in users:
+        submit(u)
+
+    if args.full:
+        # Steady-state guard: the timed window must measure the serving
+        # steady state no matter what --steps/--warmup the driver passes.
+        # The initial prefill wave of `users` x ~3.6k-token prompts needs
+        # ~users*3600/max_num_batched_tokens steps to drain, far more than
+        # a typical --warmup.  So before honoring --warmup we keep stepping
+        # until >=90% of users have completed their first round (mixed
+        # prefill-over-decode steady state), with a hard time cap as a
+        # safety net.  Only then do the driver's warmup steps run.
+        steady_target = max(1, int(0.9 * len(users)))
+        t_guard = time.perf_counter()
+        guard_cap_s = 300.0 if use_cuda else 120.0
+        guard_steps = 0
+        max_wait = max(2, int(0.05 * len(users)))
+        stable = 0
+        while True:
+            if time.perf_counter() - t_guard >= guard_cap_s:
+                break
+            ok = (len(done_once) >= steady_target
+                  and engine.scheduler.num_waiting <= max_wait)
+            stable = stable + 1 if ok else 0
+            if stable >= 20:  # equilibrium must HOLD, not just flicker
+                break
+            run_step()
+            guard_steps += 1
+        # the drain criterion exits before the ensemble's age structure is
+        # stationary: conversation resets (the expensive 3.6k-token
+        # prefills) only ramp in over ~1 conversation period (~1000 steps),
+        # so a 20-step window right after the drain read ~30% above what
+        # 60-200-step windows agree on. A fixed mixing period lets short
+        # driver windows read the converged value
+        for _ in range(mixing_steps):
+            if time.perf_counter() - t_guard >= guard_cap_s:
+                break
+            run_step()
+            guard_steps += 1
+    else:
+        # the seeded prompts still compute their last partial block: let
+        # that short wave through before the driver's warmup
+        for _ in range(64):
+            if not engine.scheduler.num_waiting:
+                break
+            run_step()
     in_steady = True
     for _ in range(args.warmup):
         run_step()
@@ -313,6 +415,25 @@ def main() -> None:
         total_tokens = t.item()
         elapsed = e.item()
 
+    if args.dump_outputs and rank == 0:
+        # one row per RequestOutput of the last timed step, in the order
+        # engine.step() returned them; ids are exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        new_ids = [t for _, o in last_outputs for t in o.new_token_ids]
+        arrays = {
+            "new_token_ids": new_ids,
+            "num_new_tokens": [len(o.new_token_ids) for _, o in last_outputs],
+            "user_id": [u.uid for u, _ in last_outputs],
+            "num_prompt_tokens": [o.num_prompt_tokens
+                                  for _, o in last_outputs],
+            "num_output_tokens": [o.num_output_tokens
+                                  for _, o in last_outputs],
+            "finished": [o.finished for _, o in last_outputs],
+        }
+        for name, vals in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                    np.asarray(vals, dtype=np.float64))
+
     if rank == 0:
         value = total_tokens / elapsed
         ttft_p50 = (
@@ -338,6 +459,7 @@ def main() -> None:
                     "data": "synthetic",
                     "ttft_p50_ms": ttft_p50,
                     "ttft_p90_ms": ttft_p90,
+                    "steady_state": "drained" if args.full else "seeded",
                     "config": {
                         "model": args.model,
                         "workload": "multi-round-qa",

@@ -3,7 +3,8 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                 "..", ".."))
 os.chdir(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-sys.argv = ["bench.py", "--gpus", "1", "--steps", "300", "--warmup", "8"]
+sys.argv = ["bench.py", "--gpus", "1", "--steps", "300", "--warmup", "8",
+            "--full"]  # watch the real drain + mixing, not the seeded start
 import time
 import bench
 from production_stack_amd.engine.engine import LLMEngine
