@@ -500,5 +500,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "8-phase deep-pipelined bf16 GEMM (out = x @ w.T)");
   m.def("skinny_gemm", &skinny_gemm,
         "Split-K MFMA GEMM for decode-shaped (M<=128) projections");
+  m.def("gemm8p_splits", &ps_gemm8p_splits,
+        "Split-K depth gemm8p picks for (M, N, K); -1 if unsupported");
+  m.def("skinny_gemm_splits", &ps_skinny_gemm_splits,
+        "Split-K depth skinny_gemm picks for (M, N, K); -1 if unsupported");
   m.def("kv_dequant", &kv_dequant, "Row-wise int8 KV dequantization");
 }

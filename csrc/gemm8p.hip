@@ -9,7 +9,8 @@
 // 16 MFMA (one C-quadrant x K=64) -> setprio(0) -> barrier}. Counted
 // s_waitcnt vmcnt(2) at the starts of phases 0 and 4 keep staged loads in
 // flight across barriers — never drained to 0 in the main loop (guide
-// T3+T4: the whole gain of the 8-phase schedule).
+// T3+T4: the whole gain of the 8-phase schedule), except at phase 4 of a
+// K-range's last iteration, where nothing newer is left to keep in flight.
 //
 // Staging schedule (phase -> half-tile), derived so every stage targets a
 // slot whose last ds_read finished a full barrier earlier (global-load->LDS
@@ -246,7 +247,13 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(
     phase(b0, 0, 1, /*B(t+1)h1*/ 3, t + 1);
     phase(b0, 1, 0, /*A(t+1)h1*/ 1, t + 1);
     phase(b0, 1, 1, /*A(t+2)h0*/ 0, t + 2);
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    // The count of 2 stands for p3's A(t+2)h0. In the last iteration that
+    // stage is skipped (t+2 == kt_end), the newest load in the FIFO is
+    // A(t+1)h1, and phases 4-7 read it: drain to 0 there.
+    if (it + 1 < n_iter)
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     phase(b1, 0, 0, /*A(t+2)h1*/ 1, t + 2);
     phase(b1, 0, 1, /*B(t+2)h0*/ 2, t + 2);
@@ -303,8 +310,9 @@ __global__ void gemm8p_combine_kernel(unsigned short* __restrict__ out,
 
 extern "C" {
 
-// Returns split count the heuristic picks (for ws sizing), or -1 if the
-// shape is unsupported (N % 256, K % 128).
+// Returns split count the heuristic picks, or -1 if the shape is
+// unsupported (N % 256, K % 128). The launched grid, the ws size and the
+// combine count all read it, and every split it counts is non-empty.
 int ps_gemm8p_splits(int M, int N, int K) {
   if (N % 256 != 0 || K % 128 != 0) return -1;
   const int mt = (M + 255) / 256;
@@ -313,6 +321,12 @@ int ps_gemm8p_splits(int M, int N, int K) {
   if (splits < 1) splits = 1;
   const int kpairs = K / 128;
   if (splits > kpairs) splits = kpairs;
+  // The kernel gives each split ceil(kpairs/splits) K-pairs, so trailing
+  // splits can come out empty; they return without writing their ws slice,
+  // which the combine kernel would still sum. Keep only the non-empty ones
+  // (a fixed point of the kernel's own per_split computation).
+  const int per_split = (kpairs + splits - 1) / splits;
+  splits = (kpairs + per_split - 1) / per_split;
   return splits;
 }
 

@@ -13,8 +13,8 @@
 //   x (tiny) is staged per 64-wide K-chunk in XOR-swizzled LDS and consumed
 //   as A-frags for ceil(M/16) m-tiles; per-k-chunk MFMA count scales with
 //   m-tiles while W traffic stays fixed.
-//   Split-K partials combine via fp32 atomicAdd into the pre-zeroed output
-//   (device-scope; SPLITS atomics per element).
+//   Split-K partials go to an fp32 workspace ws[SPLITS, M, N] and a combine
+//   kernel sums them to bf16 (no atomics; every split writes its slice).
 // mfma_f32_16x16x32_bf16; operand k-pattern as verified in
 // csrc/tools/mfma_probe.hip.
 #include "ps_common.h"
@@ -139,6 +139,12 @@ int ps_skinny_gemm_splits(int M, int N, int K) {
   int splits = target_wgs / (N / 64);
   if (splits < 1) splits = 1;
   if (splits > kchunks) splits = kchunks;
+  // The kernel gives each split ceil(kchunks/splits) chunks, so trailing
+  // splits can come out empty; they return without writing their ws slice,
+  // which the combine kernel would still sum. Keep only the non-empty ones
+  // (a fixed point of the kernel's own per_split computation).
+  const int per_split = (kchunks + splits - 1) / splits;
+  splits = (kchunks + per_split - 1) / per_split;
   return splits;
 }
 

@@ -20,7 +20,9 @@ def refcheck():
     torch.manual_seed(3)
     ok = True
     for (M, N, K) in [(256, 256, 128), (64, 256, 256), (384, 512, 384),
-                      (300, 768, 640), (1024, 1536, 896), (1, 256, 128)]:
+                      (300, 768, 640), (1024, 1536, 896), (1, 256, 128),
+                      # large K: the split count is not clamped to K/128
+                      (16, 4096, 4096), (16, 4096, 14336)]:
         x = torch.randn(M, K, dtype=torch.bfloat16, device="cuda") / 4
         w = torch.randn(N, K, dtype=torch.bfloat16, device="cuda") / 4
         got = ops.gemm8p(x, w).float().cpu()
