@@ -79,6 +79,12 @@ int ps_lora_bgmv(void* out, const void* x, const void* A, const void* B,
                  const void* scale, const void* idx, int T, int IN, int W,
                  int R, long out_stride, long x_stride, int col_off,
                  hipStream_t stream);
+int ps_fused_moe_supported(int T, int top_k, int E, int H, int I);
+int ps_fused_moe(void* out, void* offsets, void* sorted_pairs, void* act,
+                 void* y, const void* x, const void* w_gate_up,
+                 const void* w_down, const void* topk_ids, int ids_i64,
+                 const void* topk_w, int T, int top_k, int E, int H, int I,
+                 hipStream_t stream);
 }
 
 at::Tensor cachegen_encode(at::Tensor q);
@@ -427,6 +433,65 @@ void lora_bgmv(at::Tensor out, at::Tensor x, at::Tensor A, at::Tensor B,
   TORCH_CHECK(rc == 0, "lora_bgmv unsupported (R>64?) R=", R);
 }
 
+bool fused_moe_supported(int64_t T, int64_t top_k, int64_t E, int64_t H,
+                         int64_t I) {
+  const int64_t lim = 1 << 30;
+  if (T > lim || top_k > lim || E > lim || H > lim || I > lim) return false;
+  return ps_fused_moe_supported((int)T, (int)top_k, (int)E, (int)H,
+                                (int)I) != 0;
+}
+
+// scratch tensors come from the caller so they land in the graph pool
+// under capture
+void fused_moe(at::Tensor out, at::Tensor offsets, at::Tensor sorted_pairs,
+               at::Tensor act, at::Tensor y, at::Tensor x,
+               at::Tensor experts_gate_up, at::Tensor experts_down,
+               at::Tensor topk_ids, at::Tensor topk_w) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_BF16(x);
+  CHECK_GPU_BF16(experts_gate_up);
+  CHECK_GPU_BF16(experts_down);
+  CHECK_GPU_BF16(act);
+  CHECK_GPU_DTYPE(y, at::kFloat);
+  CHECK_GPU_DTYPE(offsets, at::kInt);
+  CHECK_GPU_DTYPE(sorted_pairs, at::kInt);
+  CHECK_GPU_DTYPE(topk_w, at::kFloat);
+  TORCH_CHECK(topk_ids.is_cuda() && topk_ids.is_contiguous() &&
+                  (topk_ids.scalar_type() == at::kLong ||
+                   topk_ids.scalar_type() == at::kInt),
+              "topk_ids must be contiguous int32/int64 on the GPU");
+  TORCH_CHECK(x.dim() == 2 && topk_ids.dim() == 2 &&
+                  experts_gate_up.dim() == 3 && experts_down.dim() == 3,
+              "fused_moe: x [T,H], topk_ids [T,k], gate_up [E,2I,H], "
+              "down [E,H,I]");
+  const int64_t T = x.size(0), H = x.size(1);
+  const int64_t top_k = topk_ids.size(1);
+  const int64_t E = experts_gate_up.size(0);
+  const int64_t I = experts_down.size(2);
+  TORCH_CHECK(topk_ids.size(0) == T && topk_w.dim() == 2 &&
+                  topk_w.size(0) == T && topk_w.size(1) == top_k,
+              "fused_moe: routing shape mismatch");
+  TORCH_CHECK(experts_gate_up.size(1) == 2 * I &&
+                  experts_gate_up.size(2) == H &&
+                  experts_down.size(0) == E && experts_down.size(1) == H,
+              "fused_moe: expert weight shape mismatch");
+  TORCH_CHECK(fused_moe_supported(T, top_k, E, H, I),
+              "unsupported fused_moe shape T=", T, " top_k=", top_k, " E=", E,
+              " H=", H, " I=", I);
+  const int64_t P = T * top_k;
+  TORCH_CHECK(out.numel() == T * H && offsets.numel() >= E + 1 &&
+                  sorted_pairs.numel() >= P && act.numel() >= P * I &&
+                  y.numel() >= P * H,
+              "fused_moe: output/scratch too small");
+  int rc = ps_fused_moe(
+      out.data_ptr(), offsets.data_ptr(), sorted_pairs.data_ptr(),
+      act.data_ptr(), y.data_ptr(), x.data_ptr(), experts_gate_up.data_ptr(),
+      experts_down.data_ptr(), topk_ids.data_ptr(),
+      topk_ids.scalar_type() == at::kLong ? 1 : 0, topk_w.data_ptr(), (int)T,
+      (int)top_k, (int)E, (int)H, (int)I, current_stream());
+  TORCH_CHECK(rc == 0, "fused_moe launch rejected");
+}
+
 void kv_quant(at::Tensor out, at::Tensor scales, at::Tensor in) {
   CHECK_GPU_DTYPE(out, at::kChar);
   CHECK_GPU_DTYPE(scales, at::kFloat);
@@ -505,4 +570,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_splits", &ps_skinny_gemm_splits,
         "Split-K depth skinny_gemm picks for (M, N, K); -1 if unsupported");
   m.def("kv_dequant", &kv_dequant, "Row-wise int8 KV dequantization");
+  m.def("fused_moe", &fused_moe,
+        "Grouped MoE expert MLP (align + gate_up/SiLU + down + combine)");
+  m.def("fused_moe_supported", &fused_moe_supported,
+        "Whether fused_moe accepts (T, top_k, E, H, I)");
 }

@@ -385,6 +385,11 @@ class EngineConfig:
     # weight quantization: None (bf16) or "fp8" (OCP e4m3 weights +
     # dynamic per-tensor activation quant through the fp8 MFMA pipe)
     quantization: Optional[str] = None
+    # sparse-MoE expert dispatch: "loop" (per-expert Python loop over
+    # hipBLASLt GEMMs; host syncs, so no decode hipGraphs) or "fused"
+    # (csrc/moe_fused.hip grouped kernels for steps with T*top_k <= 1024;
+    # routing stays on the device, decode hipGraphs are captured)
+    moe_backend: str = "loop"
     # draft-model speculative decoding (engine/draft.py): architecture
     # name of the (smaller, same-vocab) proposer; None = n-gram drafts
     speculative_model: Optional[str] = None

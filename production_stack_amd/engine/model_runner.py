@@ -83,6 +83,13 @@ class ModelRunner:
                 layer.lora_slots = self.lora_slots
         if config.quantization == "fp8":
             self.model.quantize_fp8()
+        if config.moe_backend not in ("loop", "fused"):
+            raise ValueError(
+                f"unknown moe_backend {config.moe_backend!r}; "
+                "expected 'loop' or 'fused'"
+            )
+        for layer in self.model.layers:
+            layer.moe_backend = config.moe_backend
         self._generator = torch.Generator(device="cpu").manual_seed(
             config.seed + 12345
         )
@@ -153,16 +160,30 @@ class ModelRunner:
 
     def capture_decode_graphs(self, max_batch: int) -> None:
         """hipGraph-capture decode-only steps (see graph_runner.py)."""
+        moe = self.model_cfg.num_experts > 0
         if (
             self.device.type != "cuda"
             or self.config.enforce_eager
             or self.pp_size > 1
             or self.config.parallel.tensor_parallel_size > 1
-            # MoE routing is data-dependent (per-expert row gathers):
-            # a captured decode graph would freeze one routing pattern
-            or self.model_cfg.num_experts > 0
+            # the MoE expert loop gathers rows on the host (data-dependent
+            # launches): a captured decode graph would freeze one routing
+            # pattern. The fused backend consumes the routing on the device.
+            or (moe and self.config.moe_backend != "fused")
         ):
             return
+        if moe:
+            # every captured bucket must fit the fused kernels' pair bound
+            max_batch = min(
+                max_batch,
+                ops.FUSED_MOE_MAX_PAIRS // self.model_cfg.num_experts_per_tok,
+            )
+            cfg = self.model_cfg
+            if not ops.fused_moe_supported(
+                max_batch, cfg.num_experts_per_tok, cfg.num_experts,
+                cfg.hidden_size, self.model.layers[0].inter,
+            ):
+                return  # the layers would fall back to the loop
         from production_stack_amd.engine.graph_runner import DecodeGraphRunner
         from production_stack_amd.ops import gemm_policy
 
@@ -170,10 +191,9 @@ class ModelRunner:
         if self.config.quantization != "fp8":
             try:
                 layer0 = self.model.layers[0]
-                weights = [
-                    layer0.qkv_proj, layer0.o_proj, layer0.gate_up_proj,
-                    layer0.down_proj,
-                ]
+                weights = [layer0.qkv_proj, layer0.o_proj]
+                if not moe:  # MoE experts run in csrc/moe_fused.hip
+                    weights += [layer0.gate_up_proj, layer0.down_proj]
                 from production_stack_amd.engine.graph_runner import BUCKETS
 
                 buckets = [b for b in BUCKETS if b <= max_batch]

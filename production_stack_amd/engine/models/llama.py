@@ -114,11 +114,14 @@ class LlamaLayer(nn.Module):
         self.o_proj = nn.Parameter(torch.empty(h, qs, dtype=torch.bfloat16))
         self.n_experts = cfg.num_experts
         self.top_k = cfg.num_experts_per_tok
+        # "loop" | "fused" (EngineConfig.moe_backend, set by ModelRunner)
+        self.moe_backend = "loop"
         if self.n_experts:
             # Mixtral-style sparse MoE: stacked per-expert projections +
-            # a top-k softmax router; each expert reuses the dense
-            # hipBLASLt GEMM + fused SiLU-mul kernels, so no new device
-            # code is involved (EP across GPUs is a round-3 item)
+            # a top-k softmax router. moe_backend "loop": each expert
+            # reuses the dense hipBLASLt GEMM + fused SiLU-mul kernels;
+            # "fused": the grouped kernels of csrc/moe_fused.hip (EP
+            # across GPUs is a round-3 item)
             self.moe_gate = nn.Parameter(
                 torch.empty(self.n_experts, h, dtype=torch.bfloat16)
             )
@@ -354,6 +357,19 @@ class LlamaLayer(nn.Module):
         probs = torch.softmax(logits, dim=-1)
         weights, sel = torch.topk(probs, self.top_k, dim=-1)
         weights = weights / weights.sum(dim=-1, keepdim=True)
+        if (
+            self.moe_backend == "fused"
+            and x.is_cuda
+            and ops.fused_moe_supported(
+                x.shape[0], self.top_k, self.n_experts, x.shape[1],
+                self.inter,
+            )
+        ):
+            # one fixed launch sequence, routing consumed on the device
+            # (csrc/moe_fused.hip); larger steps keep the loop below
+            return ops.fused_moe(
+                x, self.experts_gate_up, self.experts_down, sel, weights
+            )
         weights = weights.to(x.dtype)
         out = torch.zeros_like(x)
         for e in range(self.n_experts):

@@ -1187,9 +1187,7 @@ def handle_kv_transfer_params(app, kv_params: dict, request_id: str) -> dict:
     return out
 
 
-def main() -> None:
-    import uvicorn
-
+def build_arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(
         description="MI355X-native OpenAI-compatible serving engine"
     )
@@ -1239,6 +1237,10 @@ def main() -> None:
     ap.add_argument("--quantization", default=None,
                     choices=[None, "fp8"],
                     help="fp8 = OCP e4m3 weights through the fp8 MFMA pipe")
+    ap.add_argument("--moe-backend", default="loop",
+                    choices=["loop", "fused"],
+                    help="fused = grouped MoE expert kernels + decode "
+                         "hipGraphs for Mixtral-family models")
     ap.add_argument("--no-unified-mixed-steps", dest="unified_mixed_steps",
                     action="store_false", default=True)
     ap.add_argument("--async-scheduling", action="store_true",
@@ -1263,7 +1265,13 @@ def main() -> None:
     ap.add_argument("--runner", default=None)
     ap.add_argument("--convert", default=None)
     ap.add_argument("--trust-remote-code", action="store_true")
-    args = ap.parse_args()
+    return ap
+
+
+def main() -> None:
+    import uvicorn
+
+    args = build_arg_parser().parse_args()
     if args.kv_transfer_config:
         import json as _json
 
@@ -1302,6 +1310,7 @@ def main() -> None:
         speculative_model=args.speculative_model,
         speculative_weights_path=args.speculative_weights_path,
         quantization=args.quantization,
+        moe_backend=args.moe_backend,
         enable_lora=args.enable_lora,
         max_loras=args.max_loras,
         max_lora_rank=args.max_lora_rank,

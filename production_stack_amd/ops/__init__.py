@@ -300,6 +300,57 @@ def lora_bgmv(
     reference.lora_bgmv(out, x, A, B, scale, idx, col_off)
 
 
+FUSED_MOE_MAX_PAIRS = 1024  # T * top_k, one moe_align workgroup
+FUSED_MOE_MAX_EXPERTS = 64
+
+
+def fused_moe_supported(T: int, top_k: int, E: int, H: int, I: int) -> bool:
+    """The accept rule of csrc/moe_fused.hip (ps_fused_moe_supported):
+    decode-sized batches, 64-aligned hidden/intermediate widths."""
+    return (
+        T >= 1 and 1 <= top_k <= E <= FUSED_MOE_MAX_EXPERTS
+        and T * top_k <= FUSED_MOE_MAX_PAIRS
+        and H >= 64 and I >= 64 and H % 64 == 0 and I % 64 == 0
+    )
+
+
+def fused_moe(
+    x: torch.Tensor,
+    experts_gate_up: torch.Tensor,
+    experts_down: torch.Tensor,
+    topk_ids: torch.Tensor,
+    topk_weights: torch.Tensor,
+) -> torch.Tensor:
+    """Sparse-MoE expert MLP for routed tokens: x [T, H] bf16, gate_up
+    [E, 2I, H], down [E, H, I], topk_ids/topk_weights [T, top_k] ->
+    [T, H] bf16. On the GPU the launch sequence depends only on the shapes
+    (no host sync, no atomics): hipGraph-safe and bit-deterministic.
+    Unsupported shapes raise (see fused_moe_supported)."""
+    if x.is_cuda:
+        _require_ext()
+        T, H = x.shape
+        top_k = topk_ids.shape[1]
+        E, _, I = experts_down.shape
+        P = T * top_k
+        dev = x.device
+        # scratch via torch.empty so it lands in the graph pool under
+        # capture; the kernels overwrite every element they later read
+        out = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        sorted_pairs = torch.empty(P, dtype=torch.int32, device=dev)
+        act = torch.empty((P, I), dtype=torch.bfloat16, device=dev)
+        y = torch.empty((P, H), dtype=torch.float32, device=dev)
+        _C.fused_moe(
+            out, offsets, sorted_pairs, act, y, x, experts_gate_up,
+            experts_down, topk_ids.contiguous(),
+            topk_weights.float().contiguous(),
+        )
+        return out
+    return reference.fused_moe(
+        x, experts_gate_up, experts_down, topk_ids, topk_weights
+    )
+
+
 def fp8_linear(
     x: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor
 ) -> torch.Tensor:

@@ -200,3 +200,25 @@ def lora_bgmv(out, x, A, B, scale, idx, col_off):
             continue
         y = (A[s].float() @ x[t].float()) * float(scale[s])
         out[t, col_off : col_off + W] += (B[s].float() @ y).to(out.dtype)
+
+
+def fused_moe(x, experts_gate_up, experts_down, topk_ids, topk_weights):
+    """Reference sparse-MoE expert MLP, one (token, k) pair at a time:
+    out[t] = sum_k w[t,k] * down_e(silu(gate_e(x[t])) * up_e(x[t])) with
+    e = topk_ids[t,k]; fp32 accumulation, the SiLU-mul product rounded to
+    the activation dtype where the kernel stores it, k summed in order."""
+    import torch
+
+    T, top_k = topk_ids.shape
+    inter = experts_down.shape[2]
+    xf = x.float()
+    wts = topk_weights.float()
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for t in range(T):
+        for k in range(top_k):
+            e = int(topk_ids[t, k])
+            gu = experts_gate_up[e].float() @ xf[t]
+            act = torch.nn.functional.silu(gu[:inter]) * gu[inter:]
+            act = act.to(x.dtype).float()
+            out[t] += wts[t, k] * (experts_down[e].float() @ act)
+    return out.to(x.dtype)

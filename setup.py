@@ -39,6 +39,7 @@ ext = CUDAExtension(
         "csrc/gemm8p.hip",
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
+        "csrc/moe_fused.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
