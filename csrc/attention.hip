@@ -29,10 +29,12 @@
 // kernel runs at <10% of HBM bandwidth (measured, profiles/ run1).
 // ---------------------------------------------------------------------------
 template <int HEAD_DIM, int GQ, int BLOCK_SIZE, int NWAVES, int LOWREG,
-          typename KVT>
+          typename KVT, int PIPE = 0>
 // LOWREG: cap registers so 3 workgroups co-reside per SIMD (168-VGPR
 // budget; the fp8 instantiation otherwise lands on 170 -> 176 alloc ->
 // 2 waves and runs 36% slower despite half the KV bytes).
+// PIPE (LOWREG only): software-pipelined block loop, see below. Same loads,
+// same floating-point operations in the same order as PIPE = 0.
 __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode_kernel(
     unsigned short* __restrict__ out,            // [S, QH, HEAD_DIM]
     float* __restrict__ ws_acc,   // [S, QH, SPLITS, HD] (splits > 1)
@@ -42,6 +44,7 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
     const KVT* __restrict__ v_cache,             // [NB, KH, BS, HD]
     const int* __restrict__ block_tables,        // [S, max_blocks]
     const int* __restrict__ seq_lens,            // [S]
+    const int* __restrict__ order,               // [S] or null
     int max_blocks, float scale, int KH, long q_stride, int window) {
   using KVTr = ps_kv_traits<KVT>;
   using kvec8 = typename KVTr::vec8;
@@ -49,8 +52,14 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
   constexpr int LPG = D / 8;       // lanes per token sub-group (16 @ D=128)
   constexpr int TPW = 64 / LPG;    // tokens per wave per iteration (4)
   static_assert(BLOCK_SIZE % TPW == 0, "block size must divide");
+  static_assert(!PIPE || LOWREG, "the pipelined loop is a LOWREG variant");
 
-  const int seq = blockIdx.x;
+  // `order` (a permutation of the sequences, longest first) only changes
+  // which workgroup index serves which sequence: the hardware is observed
+  // to start workgroups in index order, so the long ones start first and
+  // the launch drains evenly. Nothing below depends on that order.
+  const int seq = order ? order[blockIdx.x] : blockIdx.x;
+  if ((unsigned)seq >= gridDim.x) return;  // not a permutation: touch nothing
   const int kvh = blockIdx.y;
   const int ctx = seq_lens[seq];
   const int wave = threadIdx.x >> 6;
@@ -103,7 +112,87 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
   // exp->mul->fma chains 4x deeper and left the kernel latency-bound at
   // <50% of HBM bandwidth (profiles/ attn_bench).
   constexpr int TPB = BLOCK_SIZE / TPW;  // tokens per sub-group per block (4)
-  for (int b = b_begin + wave; b < b_end; b += NWAVES) {
+  if constexpr (PIPE != 0) {
+    // Software-pipelined form of the loop below. That loop is one dependent
+    // chain per block: block-table entry -> address -> K/V rows -> update,
+    // two global latencies back to back that only other waves hide. Here
+    // the next block's table entry is fetched at the top of the iteration,
+    // so only the K/V latency is left on the chain. The last iteration
+    // re-fetches its own entry instead of branching, which keeps every
+    // fetch inside [b_begin, b_end). Values loaded and the order of every
+    // floating-point operation are those of the loop below.
+    // (Also holding the next block's K tile in registers was measured:
+    // 190 VGPRs, 2 waves/SIMD, 8% slower at the flagship shape.)
+    int b = b_begin + wave;
+    if (b < b_end) {
+      const int lane_off = sg * D + sl * 8;
+      // the block id is the same in every lane: keep it and the block base
+      // addresses in scalar registers
+      long blk = __builtin_amdgcn_readfirstlane(bt[b]);
+      for (; b < b_end; b += NWAVES) {
+        const long blk_next = __builtin_amdgcn_readfirstlane(
+            bt[b + NWAVES < b_end ? b + NWAVES : b]);
+        const KVT* kb = k_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
+        const KVT* vb = v_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
+        const int valid_tokens = min(BLOCK_SIZE, ctx - b * BLOCK_SIZE);
+        float sc[GQ][TPB];
+        kvec8 vv[TPB];
+#pragma unroll
+        for (int g = 0; g < GQ; g++)
+          asm volatile("" : "+v"(qp[g]));
+#pragma unroll
+        for (int tt = 0; tt < TPB; tt++) {
+          const int tok = tt * TPW + sg;
+          const bool valid =
+              tok < valid_tokens && b * BLOCK_SIZE + tok >= win_lo;
+          kvec8 kv = *(const kvec8*)(kb + tt * TPW * D + lane_off);
+          float kf[8];
+          KVTr::to_f32x8(kv, kf);
+#pragma unroll
+          for (int g = 0; g < GQ; g++) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+              s += ps_bf16_to_f32(qp[g][j]) * kf[j];
+            s = ps_group_sum<LPG>(s) * scale;
+            sc[g][tt] = valid ? s : PS_NEG_INF;
+          }
+        }
+#pragma unroll
+        for (int tt = 0; tt < TPB; tt++)
+          vv[tt] = *(const kvec8*)(vb + tt * TPW * D + lane_off);
+#pragma unroll
+        for (int g = 0; g < GQ; g++) {
+          float bmax = sc[g][0];
+#pragma unroll
+          for (int tt = 1; tt < TPB; tt++) bmax = fmaxf(bmax, sc[g][tt]);
+          const float mnew = fmaxf(m[g], bmax);
+          const float corr = __expf(m[g] - mnew);
+          float p[TPB];
+          float psum = 0.f;
+#pragma unroll
+          for (int tt = 0; tt < TPB; tt++) {
+            p[tt] = sc[g][tt] > PS_NEG_INF ? __expf(sc[g][tt] - mnew) : 0.f;
+            psum += p[tt];
+          }
+          l[g] = l[g] * corr + psum;
+#pragma unroll
+          for (int j = 0; j < 8; j++) acc[g][j] *= corr;
+#pragma unroll
+          for (int tt = 0; tt < TPB; tt++) {
+            float vf[8];
+            KVTr::to_f32x8(vv[tt], vf);
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc[g][j] += p[tt] * vf[j];
+          }
+          m[g] = mnew;
+        }
+        blk = blk_next;
+      }
+    }
+  }
+  // (the pipelined variant has run its blocks above)
+  for (int b = PIPE ? b_end : b_begin + wave; b < b_end; b += NWAVES) {
     const long blk = bt[b];
     const KVT* kb = k_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
     const KVT* vb = v_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
@@ -246,6 +335,31 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
         }
       }
     }
+  }
+}
+
+// Longest-first launch order for the decode kernel: order = indices of
+// seq_lens sorted by length descending, ties by ascending index (a stable
+// descending argsort). One workgroup ranks by counting,
+//   rank[i] = #{j : len[j] > len[i] or (len[j] == len[i] and j < i)},
+// so the ranks are a permutation of [0, S) and order[rank[i]] = i writes
+// every element exactly once: deterministic, no atomics, no host sync.
+#define PS_DECODE_ORDER_MAX 4096
+__global__ __launch_bounds__(1024) void decode_order_kernel(
+    int* __restrict__ order,           // [S]
+    const int* __restrict__ seq_lens,  // [S]
+    int S) {
+  __shared__ int lens[PS_DECODE_ORDER_MAX];
+  for (int i = threadIdx.x; i < S; i += blockDim.x) lens[i] = seq_lens[i];
+  __syncthreads();
+  for (int i = threadIdx.x; i < S; i += blockDim.x) {
+    const int li = lens[i];
+    int rank = 0;
+    for (int j = 0; j < S; j++) {
+      const int lj = lens[j];
+      rank += (lj > li || (lj == li && j < i)) ? 1 : 0;
+    }
+    order[rank] = i;
   }
 }
 
@@ -498,30 +612,37 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
                          int num_seqs, int max_blocks, float scale, int KH,
                          int GQ, int head_dim, int block_size, int num_splits,
                          long q_stride, int variant, int kv_fp8,
-                         int window, hipStream_t stream) {
+                         int window, const void* order,
+                         hipStream_t stream) {
+  if (variant < 0 || variant > 2) return -1;
   dim3 grid(num_seqs, KH, num_splits);
   constexpr int NW = 4;
   dim3 block(NW * 64);
-#define PS_DECODE_T(HD, G, BS, LR, KVT)                                      \
-  paged_attn_decode_kernel<HD, G, BS, NW, LR, KVT>                           \
+  // variant: 0 = fp32 q, 1 = low-register packed q, 2 = variant 1 with the
+  // software-pipelined block loop (next block-table entry prefetched)
+#define PS_DECODE_T(HD, G, BS, LR, KVT, PIPE)                                \
+  paged_attn_decode_kernel<HD, G, BS, NW, LR, KVT, PIPE>                     \
       <<<grid, block, 0, stream>>>(                                          \
           (unsigned short*)out, (float*)ws_acc, (float*)ws_ml,               \
           (const unsigned short*)q, (const KVT*)k_cache,                     \
           (const KVT*)v_cache, (const int*)block_tables,                     \
-          (const int*)seq_lens, max_blocks, scale, KH, q_stride, window)
+          (const int*)seq_lens, (const int*)order, max_blocks, scale, KH,    \
+          q_stride, window)
+#define PS_DECODE_V(HD, G, BS, KVT)                                          \
+  do {                                                                       \
+    if (variant == 2)                                                        \
+      PS_DECODE_T(HD, G, BS, 1, KVT, 1);                                     \
+    else if (variant == 1)                                                   \
+      PS_DECODE_T(HD, G, BS, 1, KVT, 0);                                     \
+    else                                                                     \
+      PS_DECODE_T(HD, G, BS, 0, KVT, 0);                                     \
+  } while (0)
 #define PS_DISPATCH_DECODE(HD, G, BS)                                        \
   do {                                                                       \
-    if (kv_fp8) {                                                            \
-      if (variant == 1)                                                      \
-        PS_DECODE_T(HD, G, BS, 1, unsigned char);                            \
-      else                                                                   \
-        PS_DECODE_T(HD, G, BS, 0, unsigned char);                            \
-    } else {                                                                 \
-      if (variant == 1)                                                      \
-        PS_DECODE_T(HD, G, BS, 1, unsigned short);                           \
-      else                                                                   \
-        PS_DECODE_T(HD, G, BS, 0, unsigned short);                           \
-    }                                                                        \
+    if (kv_fp8)                                                              \
+      PS_DECODE_V(HD, G, BS, unsigned char);                                 \
+    else                                                                     \
+      PS_DECODE_V(HD, G, BS, unsigned short);                                \
     if (num_splits > 1)                                                      \
       paged_attn_combine_kernel<HD>                                          \
           <<<dim3(num_seqs * KH * G), 64, 0, stream>>>(                      \
@@ -551,7 +672,19 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
   }
   return -1;
 #undef PS_DECODE_T
+#undef PS_DECODE_V
 #undef PS_DISPATCH_DECODE
+}
+
+// order[S] <- stable descending argsort of seq_lens[S]; -1 if S is outside
+// what the single-workgroup kernel handles (the caller then passes no order).
+int ps_decode_order(void* order, const void* seq_lens, int S,
+                    hipStream_t stream) {
+  if (S < 1 || S > PS_DECODE_ORDER_MAX) return -1;
+  const int threads = S <= 256 ? 256 : 1024;
+  decode_order_kernel<<<1, threads, 0, stream>>>((int*)order,
+                                                 (const int*)seq_lens, S);
+  return 0;
 }
 
 int ps_paged_attn_prefill(void* out, const void* q, const void* k_cache,

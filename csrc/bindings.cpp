@@ -35,7 +35,9 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
                          int num_seqs, int max_blocks, float scale, int KH,
                          int GQ, int head_dim, int block_size, int num_splits,
                          long q_stride, int variant, int kv_fp8, int window,
-                         hipStream_t stream);
+                         const void* order, hipStream_t stream);
+int ps_decode_order(void* order, const void* seq_lens, int S,
+                    hipStream_t stream);
 int ps_prefill_mfma32_splits(int num_tiles, int KH, int GQ);
 int ps_paged_attn_prefill_mfma32(void* out, void* ws_o, void* ws_ml,
                                  long q_tokens, const void* q,
@@ -175,13 +177,23 @@ void rotary_embedding(at::Tensor positions, at::Tensor q, at::Tensor k,
 void paged_attn_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
                        at::Tensor v_cache, at::Tensor block_tables,
                        at::Tensor seq_lens, double scale, int64_t num_splits,
-                       int64_t variant, int64_t window) {
+                       int64_t variant, int64_t window,
+                       c10::optional<at::Tensor> order) {
   CHECK_GPU_BF16(out);
   const int kv_fp8 = cache_fp8(k_cache);
   cache_fp8(v_cache);
   CHECK_GPU_DTYPE(block_tables, at::kInt);
   CHECK_GPU_DTYPE(seq_lens, at::kInt);
   const int S = (int)q.size(0);
+  // launch order of the sequences (ops.decode_order): a permutation of
+  // [0, S). The kernel skips entries outside [0, S).
+  const void* order_p = nullptr;
+  if (order.has_value()) {
+    const at::Tensor& order_t = *order;
+    CHECK_GPU_DTYPE(order_t, at::kInt);
+    TORCH_CHECK(order_t.numel() == S, "order must have one entry per seq");
+    order_p = order_t.data_ptr();
+  }
   const int QH = (int)q.size(1);
   const int HD = (int)q.size(2);
   const int KH = (int)k_cache.size(1);
@@ -208,10 +220,20 @@ void paged_attn_decode(at::Tensor out, at::Tensor q, at::Tensor k_cache,
       out.data_ptr(), acc_p, ml_p, q.data_ptr(), k_cache.data_ptr(),
       v_cache.data_ptr(), block_tables.data_ptr(), seq_lens.data_ptr(), S,
       max_blocks, (float)scale, KH, GQ, HD, BS, (int)num_splits,
-      q_row_stride(q, HD), (int)variant, kv_fp8, (int)window,
+      q_row_stride(q, HD), (int)variant, kv_fp8, (int)window, order_p,
       current_stream());
   TORCH_CHECK(rc == 0, "unsupported decode config: head_dim=", HD,
-              " block_size=", BS, " gqa=", GQ);
+              " block_size=", BS, " gqa=", GQ, " variant=", variant);
+}
+
+// order <- stable descending argsort of seq_lens; false (order untouched)
+// when S is outside what the kernel handles
+bool decode_order(at::Tensor order, at::Tensor seq_lens) {
+  CHECK_GPU_DTYPE(order, at::kInt);
+  CHECK_GPU_DTYPE(seq_lens, at::kInt);
+  TORCH_CHECK(order.numel() == seq_lens.numel(), "order/seq_lens size");
+  return ps_decode_order(order.data_ptr(), seq_lens.data_ptr(),
+                         (int)seq_lens.numel(), current_stream()) == 0;
 }
 
 void paged_attn_prefill(at::Tensor out, at::Tensor q, at::Tensor k_cache,
@@ -536,7 +558,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("v_cache"), pybind11::arg("block_tables"),
         pybind11::arg("seq_lens"), pybind11::arg("scale"),
         pybind11::arg("num_splits") = 0, pybind11::arg("variant") = 0,
-        pybind11::arg("window") = 0);
+        pybind11::arg("window") = 0,
+        pybind11::arg("order") = pybind11::none());
+  m.def("decode_order", &decode_order,
+        "Longest-first sequence order for paged_attn_decode");
   m.def("paged_attn_prefill", &paged_attn_prefill,
         "Paged attention, chunked prefill (bf16 KV)");
   m.def("lora_bgmv", &lora_bgmv,

@@ -74,7 +74,76 @@ def bench_decode(batch=64, ctx=1024, qh=32, kh=8, hd=128, iters=50,
           f"{dt*1e6:.1f} us  {bytes_kv/dt/1e9:.0f} GB/s")
 
 
+def bench_decode_ragged(batch=312, lo=3600, hi=5600, qh=32, kh=8, hd=128,
+                        iters=50, variant=1, order=False, seed=0,
+                        uniform=False):
+    """The flagship decode shape: `batch` sequences with context lengths
+    uniform in [lo, hi] in shuffled (batch) order, or with uniform=True the
+    same total token count at equal lengths. The gap between the two is what
+    the launch's tail costs; order=True launches longest first
+    (ops.decode_order). Returns the time per call in seconds."""
+    from production_stack_amd import ops
+    bs = 16
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(lo, hi + 1, (batch,), generator=g)
+    if uniform:
+        total = int(lens.sum())
+        lens = torch.full((batch,), total // batch)
+        lens[: total % batch] += 1
+    per = (int(lens.max()) + bs - 1) // bs
+    nb = batch * per + 1
+    k = torch.randn(nb, kh, bs, hd, dtype=torch.bfloat16, device="cuda")
+    v = torch.randn_like(k)
+    # shuffled block tables: physical blocks in no particular order
+    bt = (torch.randperm(batch * per, generator=g) + 1).to(torch.int32)
+    bt = bt.reshape(batch, per).cuda()
+    sl = lens.to(torch.int32).cuda()
+    q = torch.randn(batch, qh, hd, dtype=torch.bfloat16, device="cuda")
+    out = torch.empty_like(q)
+    scale = hd ** -0.5
+
+    def call():
+        if order:  # sorted on every call, as the model's forward does
+            _C.paged_attn_decode(out, q, k, v, bt, sl, scale, 0, variant, 0,
+                                 ops.decode_order(sl))
+        else:
+            _C.paged_attn_decode(out, q, k, v, bt, sl, scale, 0, variant)
+
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        call()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / iters
+    bytes_kv = int(lens.sum()) * kh * hd * 2 * 2
+    print(f"decode v{variant} b={batch} "
+          f"{'uniform' if uniform else 'ragged'}[{lo},{hi}]"
+          f"{' longest-first' if order else ''}: "
+          f"{dt*1e6:.1f} us  {bytes_kv/dt/1e9:.0f} GB/s")
+    return dt
+
+
+def ragged_report(variants=(1,), order_modes=(False,), repeats=3):
+    """Ragged vs uniform at the flagship shape, `repeats` interleaved rounds
+    per configuration."""
+    for _ in range(repeats):
+        for v in variants:
+            bench_decode_ragged(variant=v, uniform=True)
+            for o in order_modes:
+                bench_decode_ragged(variant=v, order=o)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "ragged":
+        # attn_bench.py ragged [variants, e.g. 1,2] [order: 0, 1 or 0,1]
+        vs = tuple(int(x) for x in sys.argv[2].split(",")) \
+            if len(sys.argv) > 2 else (1, 2)
+        om = tuple(bool(int(x)) for x in sys.argv[3].split(",")) \
+            if len(sys.argv) > 3 else (False, True)
+        ragged_report(vs, om)
+        sys.exit(0)
     for v in (3, 4):
         for ctx in (1024, 2048, 4096):
             bench_prefill(ctx, variant=v)

@@ -63,6 +63,19 @@ class BatchMeta:
         self.lora_idx = lora_idx
         self.mm_rows = mm_rows
         self.mm_embeds = mm_embeds
+        # longest-first launch order of the decode sequences; the model's
+        # forward sets it anew on every call (never carried between calls:
+        # a captured graph must recompute it from the live seq_lens)
+        self.decode_order: Optional[torch.Tensor] = None
+
+
+def _decode_order_wanted(meta: BatchMeta) -> bool:
+    """The launch order only pays on the GPU (the CPU reference ignores it)."""
+    return (
+        ops.DECODE_ORDER
+        and meta.num_decode_seqs > 0
+        and meta.decode_seq_lens.is_cuda
+    )
 
 
 def build_cos_sin_cache(
@@ -277,6 +290,7 @@ class LlamaLayer(nn.Module):
                     meta.decode_seq_lens,
                     self.scale,
                     self.window,
+                    meta.decode_order,
                 )
             )
         attn = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
@@ -513,6 +527,12 @@ class LlamaForCausalLM(nn.Module):
             residual = None
         else:
             hidden = token_ids  # mid-pipeline: activations from prev stage
+        # one sort per forward, shared by every layer; computed here on
+        # every call so that a hipGraph capture of this forward records the
+        # sort and each replay orders by the live seq_lens
+        meta.decode_order = None
+        if _decode_order_wanted(meta):
+            meta.decode_order = ops.decode_order(meta.decode_seq_lens)
         for layer, cache in zip(self.layers, kv_caches):
             hidden, residual = layer(
                 hidden, residual, meta, cache, self.cos_sin

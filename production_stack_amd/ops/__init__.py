@@ -9,6 +9,7 @@ the engine and its tests work in GPU-less CI.
 from __future__ import annotations
 
 import os
+from typing import Optional
 
 import torch
 
@@ -112,6 +113,16 @@ def reshape_and_cache(
     reference.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
 
 
+# Decode attention kernel variant (csrc/attention.hip): 2 = the low-register
+# packed-q kernel (variant 1) with the next block-table entry prefetched,
+# bit-identical to it and 1.2% faster at the flagship ragged shape
+# (profiles/README.md). PS_DECODE_VARIANT=1 restores variant 1 for A/B.
+DECODE_VARIANT = int(os.environ.get("PS_DECODE_VARIANT", "2"))
+# Longest-first launch order for decode attention (decode_order), computed
+# by the model once per forward; PS_DECODE_ORDER=0 turns it off for A/B.
+DECODE_ORDER = os.environ.get("PS_DECODE_ORDER", "1") != "0"
+
+
 def paged_attn_decode(
     q: torch.Tensor,
     k_cache: torch.Tensor,
@@ -120,20 +131,41 @@ def paged_attn_decode(
     seq_lens: torch.Tensor,
     scale: float,
     window: int = 0,
+    order: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
+    """`order` (see decode_order) only changes the order in which the GPU
+    kernel's workgroups are launched, never a result; the CPU reference
+    ignores it."""
     if q.is_cuda:
         _require_ext()
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        # variant 1 = low-register packed-q kernel (3 waves/SIMD): measured
-        # +17-26% over variant 0 across batch/ctx (profiles/attn_bench).
+        # variants 1/2 = low-register packed-q kernel (3 waves/SIMD):
+        # measured +17-26% over variant 0 across batch/ctx
+        # (profiles/attn_bench).
         _C.paged_attn_decode(
-            out, q, k_cache, v_cache, block_tables, seq_lens, scale, 0, 1,
-            window
+            out, q, k_cache, v_cache, block_tables, seq_lens, scale, 0,
+            DECODE_VARIANT, window, order
         )
         return out
     return reference.paged_attn_decode(
         q, k_cache, v_cache, block_tables, seq_lens, scale, window
     )
+
+
+def decode_order(seq_lens: torch.Tensor) -> Optional[torch.Tensor]:
+    """Indices of `seq_lens` (int32 [S]) sorted longest first, ties by
+    ascending index (a stable descending argsort), as int32 [S]: the launch
+    order for paged_attn_decode, so that a ragged batch starts its long
+    sequences first and the launch drains evenly. On the GPU one small
+    kernel with no host sync (hipGraph-safe); returns None when S is more
+    than that kernel handles, and the caller then passes no order."""
+    if seq_lens.is_cuda:
+        _require_ext()
+        order = torch.empty_like(seq_lens)
+        if not _C.decode_order(order, seq_lens):
+            return None
+        return order
+    return torch.argsort(-seq_lens, stable=True).int()
 
 
 def paged_attn_prefill(
