@@ -33,8 +33,11 @@ template <int HEAD_DIM, int GQ, int BLOCK_SIZE, int NWAVES, int LOWREG,
 // LOWREG: cap registers so 3 workgroups co-reside per SIMD (168-VGPR
 // budget; the fp8 instantiation otherwise lands on 170 -> 176 alloc ->
 // 2 waves and runs 36% slower despite half the KV bytes).
-// PIPE (LOWREG only): software-pipelined block loop, see below. Same loads,
-// same floating-point operations in the same order as PIPE = 0.
+// PIPE (LOWREG only): software-pipelined block loop, see below. PIPE 1: same
+// loads, same floating-point operations in the same order as PIPE = 0.
+// PIPE 2 (bf16 KV): PIPE 1 with the next block's K tile prefetched and the
+// score reduction on the DPP path (ps_row_sum16); the same floating-point
+// operations in the same order again, so all three are bit-identical.
 __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode_kernel(
     unsigned short* __restrict__ out,            // [S, QH, HEAD_DIM]
     float* __restrict__ ws_acc,   // [S, QH, SPLITS, HD] (splits > 1)
@@ -53,6 +56,8 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
   constexpr int TPW = 64 / LPG;    // tokens per wave per iteration (4)
   static_assert(BLOCK_SIZE % TPW == 0, "block size must divide");
   static_assert(!PIPE || LOWREG, "the pipelined loop is a LOWREG variant");
+  static_assert(PIPE < 2 || sizeof(KVT) == 2, "PIPE 2 is built for bf16 KV");
+  constexpr bool KPRE = PIPE == 2;  // next block's K tile held in registers
 
   // `order` (a permutation of the sequences, longest first) only changes
   // which workgroup index serves which sequence: the hardware is observed
@@ -121,22 +126,44 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
     // re-fetches its own entry instead of branching, which keeps every
     // fetch inside [b_begin, b_end). Values loaded and the order of every
     // floating-point operation are those of the loop below.
-    // (Also holding the next block's K tile in registers was measured:
-    // 190 VGPRs, 2 waves/SIMD, 8% slower at the flagship shape.)
+    // PIPE 2 also holds the next block's K tile, packed, in registers and
+    // fetches the table two blocks ahead. Tried with the XOR-shuffle score
+    // reduction it spilled (190 VGPRs unspilled, 2 waves/SIMD, 8% slower);
+    // with the DPP reduction it builds at 168 VGPRs without scratch.
     int b = b_begin + wave;
     if (b < b_end) {
       const int lane_off = sg * D + sl * 8;
+      const long tile = (long)BLOCK_SIZE * D;
       // the block id is the same in every lane: keep it and the block base
       // addresses in scalar registers
       long blk = __builtin_amdgcn_readfirstlane(bt[b]);
-      for (; b < b_end; b += NWAVES) {
-        const long blk_next = __builtin_amdgcn_readfirstlane(
+      long blk_next = 0;
+      kvec8 kc[TPB];  // KPRE: this block's K rows, loaded an iteration ago
+      if constexpr (KPRE) {
+        blk_next = __builtin_amdgcn_readfirstlane(
             bt[b + NWAVES < b_end ? b + NWAVES : b]);
-        const KVT* kb = k_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
-        const KVT* vb = v_cache + ((blk * KH + kvh) * BLOCK_SIZE) * D;
+#pragma unroll
+        for (int tt = 0; tt < TPB; tt++)
+          kc[tt] = *(const kvec8*)(k_cache + (blk * KH + kvh) * tile +
+                                   tt * TPW * D + lane_off);
+      }
+      for (; b < b_end; b += NWAVES) {
+        // KPRE runs the table two blocks ahead and K one block ahead
+        const int b_pre = b + (KPRE ? 2 : 1) * NWAVES;
+        const long blk_pre =
+            __builtin_amdgcn_readfirstlane(bt[b_pre < b_end ? b_pre : b]);
+        const KVT* kb = k_cache + (blk * KH + kvh) * tile;
+        const KVT* vb = v_cache + (blk * KH + kvh) * tile;
         const int valid_tokens = min(BLOCK_SIZE, ctx - b * BLOCK_SIZE);
         float sc[GQ][TPB];
         kvec8 vv[TPB];
+        kvec8 kn[TPB];
+        if constexpr (KPRE) {
+          const KVT* kbn = k_cache + (blk_next * KH + kvh) * tile;
+#pragma unroll
+          for (int tt = 0; tt < TPB; tt++)
+            kn[tt] = *(const kvec8*)(kbn + tt * TPW * D + lane_off);
+        }
 #pragma unroll
         for (int g = 0; g < GQ; g++)
           asm volatile("" : "+v"(qp[g]));
@@ -145,7 +172,11 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
           const int tok = tt * TPW + sg;
           const bool valid =
               tok < valid_tokens && b * BLOCK_SIZE + tok >= win_lo;
-          kvec8 kv = *(const kvec8*)(kb + tt * TPW * D + lane_off);
+          kvec8 kv;
+          if constexpr (KPRE)
+            kv = kc[tt];
+          else
+            kv = *(const kvec8*)(kb + tt * TPW * D + lane_off);
           float kf[8];
           KVTr::to_f32x8(kv, kf);
 #pragma unroll
@@ -154,40 +185,84 @@ __global__ __launch_bounds__(NWAVES * 64, LOWREG ? 3 : 1) void paged_attn_decode
 #pragma unroll
             for (int j = 0; j < 8; j++)
               s += ps_bf16_to_f32(qp[g][j]) * kf[j];
-            s = ps_group_sum<LPG>(s) * scale;
+            if constexpr (PIPE == 2 && LPG == 16)
+              s = ps_row_sum16(s) * scale;
+            else
+              s = ps_group_sum<LPG>(s) * scale;
             sc[g][tt] = valid ? s : PS_NEG_INF;
           }
         }
 #pragma unroll
         for (int tt = 0; tt < TPB; tt++)
           vv[tt] = *(const kvec8*)(vb + tt * TPW * D + lane_off);
+        if constexpr (PIPE >= 2) {
+          // Same operations per (head, dim) in the same order as below, with
+          // the token loop outside the head loop: V is widened once per
+          // token, not once per (token, head). sc is reused to hold p.
 #pragma unroll
-        for (int g = 0; g < GQ; g++) {
-          float bmax = sc[g][0];
+          for (int g = 0; g < GQ; g++) {
+            float bmax = sc[g][0];
 #pragma unroll
-          for (int tt = 1; tt < TPB; tt++) bmax = fmaxf(bmax, sc[g][tt]);
-          const float mnew = fmaxf(m[g], bmax);
-          const float corr = __expf(m[g] - mnew);
-          float p[TPB];
-          float psum = 0.f;
+            for (int tt = 1; tt < TPB; tt++) bmax = fmaxf(bmax, sc[g][tt]);
+            const float mnew = fmaxf(m[g], bmax);
+            const float corr = __expf(m[g] - mnew);
+            float psum = 0.f;
 #pragma unroll
-          for (int tt = 0; tt < TPB; tt++) {
-            p[tt] = sc[g][tt] > PS_NEG_INF ? __expf(sc[g][tt] - mnew) : 0.f;
-            psum += p[tt];
+            for (int tt = 0; tt < TPB; tt++) {
+              sc[g][tt] =
+                  sc[g][tt] > PS_NEG_INF ? __expf(sc[g][tt] - mnew) : 0.f;
+              psum += sc[g][tt];
+            }
+            l[g] = l[g] * corr + psum;
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc[g][j] *= corr;
+            m[g] = mnew;
           }
-          l[g] = l[g] * corr + psum;
-#pragma unroll
-          for (int j = 0; j < 8; j++) acc[g][j] *= corr;
 #pragma unroll
           for (int tt = 0; tt < TPB; tt++) {
             float vf[8];
             KVTr::to_f32x8(vv[tt], vf);
 #pragma unroll
-            for (int j = 0; j < 8; j++) acc[g][j] += p[tt] * vf[j];
+            for (int g = 0; g < GQ; g++)
+#pragma unroll
+              for (int j = 0; j < 8; j++) acc[g][j] += sc[g][tt] * vf[j];
           }
-          m[g] = mnew;
+        } else {
+#pragma unroll
+          for (int g = 0; g < GQ; g++) {
+            float bmax = sc[g][0];
+#pragma unroll
+            for (int tt = 1; tt < TPB; tt++) bmax = fmaxf(bmax, sc[g][tt]);
+            const float mnew = fmaxf(m[g], bmax);
+            const float corr = __expf(m[g] - mnew);
+            float p[TPB];
+            float psum = 0.f;
+#pragma unroll
+            for (int tt = 0; tt < TPB; tt++) {
+              p[tt] = sc[g][tt] > PS_NEG_INF ? __expf(sc[g][tt] - mnew) : 0.f;
+              psum += p[tt];
+            }
+            l[g] = l[g] * corr + psum;
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc[g][j] *= corr;
+#pragma unroll
+            for (int tt = 0; tt < TPB; tt++) {
+              float vf[8];
+              KVTr::to_f32x8(vv[tt], vf);
+#pragma unroll
+              for (int j = 0; j < 8; j++) acc[g][j] += p[tt] * vf[j];
+            }
+            m[g] = mnew;
+          }
         }
-        blk = blk_next;
+        if constexpr (KPRE) {
+#pragma unroll
+          for (int tt = 0; tt < TPB; tt++) kc[tt] = kn[tt];
+          blk = blk_next;
+          blk_next = blk_pre;
+        } else {
+          blk = blk_pre;
+        }
       }
     }
   }
@@ -614,12 +689,15 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
                          long q_stride, int variant, int kv_fp8,
                          int window, const void* order,
                          hipStream_t stream) {
-  if (variant < 0 || variant > 2) return -1;
+  if (variant < 0 || variant > 3) return -1;
+  if (kv_fp8 && variant > 2) variant = 2;  // variant 3 is built for bf16 KV
   dim3 grid(num_seqs, KH, num_splits);
   constexpr int NW = 4;
   dim3 block(NW * 64);
   // variant: 0 = fp32 q, 1 = low-register packed q, 2 = variant 1 with the
-  // software-pipelined block loop (next block-table entry prefetched)
+  // software-pipelined block loop (next block-table entry prefetched),
+  // 3 = variant 2 with the next block's K tile prefetched and the score
+  // reduction in DPP (bf16 KV only; an fp8 cache runs variant 2)
 #define PS_DECODE_T(HD, G, BS, LR, KVT, PIPE)                                \
   paged_attn_decode_kernel<HD, G, BS, NW, LR, KVT, PIPE>                     \
       <<<grid, block, 0, stream>>>(                                          \
@@ -641,6 +719,8 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
   do {                                                                       \
     if (kv_fp8)                                                              \
       PS_DECODE_V(HD, G, BS, unsigned char);                                 \
+    else if (variant == 3)                                                   \
+      PS_DECODE_T(HD, G, BS, 1, unsigned short, 2);                          \
     else                                                                     \
       PS_DECODE_V(HD, G, BS, unsigned short);                                \
     if (num_splits > 1)                                                      \

@@ -47,6 +47,24 @@ PS_DEV float ps_group_sum(float v) {
   return v;
 }
 
+// ps_group_sum<16> without the LDS crossbar: lane i adds lane (i + k) % 16 of
+// its 16-lane row for k = 8, 4, 2, 1. After the steps before it that lane
+// holds the value of lane i ^ k, so every sum is the one the XOR tree forms
+// and the result is bit-identical. Every source lane of a row rotation is
+// live, so bound_ctrl changes no value; it lets the compiler fold the move.
+PS_DEV float ps_row_sum16(float v) {
+#define PS_ROW_ROR_ADD(K)                                                    \
+  v += __builtin_bit_cast(                                                   \
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),      \
+                                         0x120 + (K), 0xf, 0xf, true))
+  PS_ROW_ROR_ADD(8);
+  PS_ROW_ROR_ADD(4);
+  PS_ROW_ROR_ADD(2);
+  PS_ROW_ROR_ADD(1);
+#undef PS_ROW_ROR_ADD
+  return v;
+}
+
 template <int WIDTH>
 PS_DEV float ps_group_max(float v) {
 #pragma unroll

@@ -76,12 +76,15 @@ def bench_decode(batch=64, ctx=1024, qh=32, kh=8, hd=128, iters=50,
 
 def bench_decode_ragged(batch=312, lo=3600, hi=5600, qh=32, kh=8, hd=128,
                         iters=50, variant=1, order=False, seed=0,
-                        uniform=False):
+                        uniform=False, shared_blocks=0):
     """The flagship decode shape: `batch` sequences with context lengths
     uniform in [lo, hi] in shuffled (batch) order, or with uniform=True the
     same total token count at equal lengths. The gap between the two is what
     the launch's tail costs; order=True launches longest first
-    (ops.decode_order). Returns the time per call in seconds."""
+    (ops.decode_order). shared_blocks > 0 points the first that many table
+    entries of every sequence at the same physical blocks, as prefix caching
+    does for the flagship's shared system prompt (62 blocks). Returns the
+    time per call in seconds."""
     from production_stack_amd import ops
     bs = 16
     g = torch.Generator().manual_seed(seed)
@@ -96,7 +99,10 @@ def bench_decode_ragged(batch=312, lo=3600, hi=5600, qh=32, kh=8, hd=128,
     v = torch.randn_like(k)
     # shuffled block tables: physical blocks in no particular order
     bt = (torch.randperm(batch * per, generator=g) + 1).to(torch.int32)
-    bt = bt.reshape(batch, per).cuda()
+    bt = bt.reshape(batch, per)
+    if shared_blocks:
+        bt[:, :shared_blocks] = bt[0, :shared_blocks].clone()
+    bt = bt.cuda()
     sl = lens.to(torch.int32).cuda()
     q = torch.randn(batch, qh, hd, dtype=torch.bfloat16, device="cuda")
     out = torch.empty_like(q)
@@ -120,7 +126,8 @@ def bench_decode_ragged(batch=312, lo=3600, hi=5600, qh=32, kh=8, hd=128,
     bytes_kv = int(lens.sum()) * kh * hd * 2 * 2
     print(f"decode v{variant} b={batch} "
           f"{'uniform' if uniform else 'ragged'}[{lo},{hi}]"
-          f"{' longest-first' if order else ''}: "
+          f"{' longest-first' if order else ''}"
+          f"{f' shared-prefix {shared_blocks} blocks' if shared_blocks else ''}: "
           f"{dt*1e6:.1f} us  {bytes_kv/dt/1e9:.0f} GB/s")
     return dt
 
@@ -133,6 +140,8 @@ def ragged_report(variants=(1,), order_modes=(False,), repeats=3):
             bench_decode_ragged(variant=v, uniform=True)
             for o in order_modes:
                 bench_decode_ragged(variant=v, order=o)
+            bench_decode_ragged(variant=v, order=order_modes[-1],
+                                shared_blocks=62)
 
 
 if __name__ == "__main__":

@@ -250,6 +250,20 @@ class LlamaLayer(nn.Module):
             qh = q.view(T, self.q_heads, self.head_dim)
         outs: List[torch.Tensor] = []
         tp = meta.num_prefill_tokens
+        # mixed step on the GPU: both kernels write their rows of one buffer,
+        # which saves a concatenation of the two results in every layer
+        buf = None
+        if (
+            qh.is_cuda
+            and 0 < tp < T
+            and meta.num_decode_seqs > 0
+            and self.head_dim == 128
+            and meta.prefill_tiles is not None
+        ):
+            buf = torch.empty(
+                (T, self.q_heads, self.head_dim),
+                dtype=qh.dtype, device=qh.device,
+            )
         if tp > 0:
             if (
                 qh.is_cuda
@@ -265,6 +279,7 @@ class LlamaLayer(nn.Module):
                         meta.prefill_tiles,
                         self.scale,
                         self.window,
+                        out=None if buf is None else buf[:tp],
                     )
                 )
             else:
@@ -291,9 +306,13 @@ class LlamaLayer(nn.Module):
                     self.scale,
                     self.window,
                     meta.decode_order,
+                    **({} if buf is None else {"out": buf[tp:]}),
                 )
             )
-        attn = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
+        if buf is not None:
+            attn = buf
+        else:
+            attn = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
         if getattr(self, "fp8_w", None) is not None:
             attn_out = ops.fp8_linear(attn.reshape(T, qs),
                                       *self.fp8_w["o"])

@@ -113,14 +113,31 @@ def reshape_and_cache(
     reference.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
 
 
-# Decode attention kernel variant (csrc/attention.hip): 2 = the low-register
-# packed-q kernel (variant 1) with the next block-table entry prefetched,
-# bit-identical to it and 1.2% faster at the flagship ragged shape
-# (profiles/README.md). PS_DECODE_VARIANT=1 restores variant 1 for A/B.
-DECODE_VARIANT = int(os.environ.get("PS_DECODE_VARIANT", "2"))
+# Decode attention kernel variant (csrc/attention.hip): 3 = the low-register
+# packed-q kernel with the next block's K tile and the block-table entry two
+# blocks ahead prefetched and the score reduction in DPP instead of LDS
+# shuffles; bit-identical to variants 1 and 2, 2% faster than variant 2 at
+# the flagship ragged shape and 8% where the batch shares a cached prompt
+# prefix (profiles/README.md). An fp8 KV cache runs variant 2 = variant 1
+# with the next block-table entry prefetched. PS_DECODE_VARIANT=2 (or 1)
+# restores those for A/B.
+DECODE_VARIANT = int(os.environ.get("PS_DECODE_VARIANT", "3"))
 # Longest-first launch order for decode attention (decode_order), computed
 # by the model once per forward; PS_DECODE_ORDER=0 turns it off for A/B.
 DECODE_ORDER = os.environ.get("PS_DECODE_ORDER", "1") != "0"
+
+
+def _check_out(out: torch.Tensor, q: torch.Tensor) -> None:
+    """An attention `out=` buffer is written as dense [T, QH, HD] rows."""
+    if (
+        out.shape != q.shape
+        or out.dtype != q.dtype
+        or out.device != q.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(
+            "out must be contiguous with q's shape, dtype and device"
+        )
 
 
 def paged_attn_decode(
@@ -132,24 +149,34 @@ def paged_attn_decode(
     scale: float,
     window: int = 0,
     order: Optional[torch.Tensor] = None,
+    out: Optional[torch.Tensor] = None,
+    variant: Optional[int] = None,
 ) -> torch.Tensor:
     """`order` (see decode_order) only changes the order in which the GPU
     kernel's workgroups are launched, never a result; the CPU reference
-    ignores it."""
+    ignores it. `out` (contiguous, q's shape and dtype) receives the result
+    and is returned; `variant` overrides DECODE_VARIANT for this call."""
+    if out is not None:
+        _check_out(out, q)
     if q.is_cuda:
         _require_ext()
-        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        # variants 1/2 = low-register packed-q kernel (3 waves/SIMD):
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        # variants 1-3 = low-register packed-q kernel (3 waves/SIMD):
         # measured +17-26% over variant 0 across batch/ctx
         # (profiles/attn_bench).
         _C.paged_attn_decode(
             out, q, k_cache, v_cache, block_tables, seq_lens, scale, 0,
-            DECODE_VARIANT, window, order
+            DECODE_VARIANT if variant is None else variant, window, order
         )
         return out
-    return reference.paged_attn_decode(
+    res = reference.paged_attn_decode(
         q, k_cache, v_cache, block_tables, seq_lens, scale, window
     )
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
 
 
 def decode_order(seq_lens: torch.Tensor) -> Optional[torch.Tensor]:
@@ -220,12 +247,16 @@ def paged_attn_prefill_mfma(
     scale: float,
     window: int = 0,
     variant: int = None,
+    out: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """MFMA-tiled chunked prefill (GPU, head_dim 128 only). tile_info rows
     must be built with n_rows <= prefill_tile_rows() for the active
-    variant."""
+    variant. `out` (contiguous, q's shape and dtype) receives the result."""
     _require_ext()
-    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    else:
+        _check_out(out, q)
     # v5's split-KV (up to 8 kv-splits) keeps CUs filled at small
     # serving launches, where it now beats v3 at the canonical shapes
     # (12-seq x 200-row continuation at hist 4600: 305 vs 263 TF; fresh
