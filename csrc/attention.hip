@@ -619,6 +619,10 @@ __global__ void reshape_and_cache_kernel(
 // Greedy sampling: argmax over the vocab per row.
 //   grid = (num_rows), block = 256
 // ---------------------------------------------------------------------------
+// VEC: every row starts on a 16-byte boundary (V % 8 == 0 and an aligned
+// base), so a thread reads 8 logits per load. Otherwise rows after the first
+// start off that boundary and the row is read one element at a time.
+template <bool VEC>
 __global__ void greedy_sample_kernel(long* __restrict__ out,  // [R]
                                      const unsigned short* __restrict__ logits,
                                      int V) {
@@ -626,24 +630,25 @@ __global__ void greedy_sample_kernel(long* __restrict__ out,  // [R]
   const unsigned short* row = logits + r * (long)V;
   float best = PS_NEG_INF;
   int besti = 0;
-  for (int i = threadIdx.x * 8; i + 8 <= V; i += blockDim.x * 8) {
-    ps_bf16x8 xv = *(const ps_bf16x8*)(row + i);
+  if (VEC) {
+    for (int i = threadIdx.x * 8; i + 8 <= V; i += blockDim.x * 8) {
+      ps_bf16x8 xv = *(const ps_bf16x8*)(row + i);
 #pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const float f = ps_bf16_to_f32(xv[j]);
-      if (f > best) {
-        best = f;
-        besti = i + j;
+      for (int j = 0; j < 8; j++) {
+        const float f = ps_bf16_to_f32(xv[j]);
+        if (f > best) {
+          best = f;
+          besti = i + j;
+        }
       }
     }
-  }
-  // tail (V not multiple of 8*block)
-  const int tail_start = (V / 8) * 8;
-  for (int i = tail_start + threadIdx.x; i < V; i += blockDim.x) {
-    const float f = ps_bf16_to_f32(row[i]);
-    if (f > best) {
-      best = f;
-      besti = i;
+  } else {
+    for (int i = threadIdx.x; i < V; i += blockDim.x) {
+      const float f = ps_bf16_to_f32(row[i]);
+      if (f > best) {
+        best = f;
+        besti = i;
+      }
     }
   }
   // wave reduce keeping the smallest index among ties
@@ -816,8 +821,13 @@ void ps_reshape_and_cache(const void* k, const void* v, void* k_cache,
 
 void ps_greedy_sample(void* out, const void* logits, long R, int V,
                       hipStream_t stream) {
-  greedy_sample_kernel<<<dim3((unsigned)R), 256, 0, stream>>>(
-      (long*)out, (const unsigned short*)logits, V);
+  if (R <= 0 || V <= 0) return;
+  if (V % 8 == 0 && (uintptr_t)logits % 16 == 0)
+    greedy_sample_kernel<true><<<dim3((unsigned)R), 256, 0, stream>>>(
+        (long*)out, (const unsigned short*)logits, V);
+  else
+    greedy_sample_kernel<false><<<dim3((unsigned)R), 256, 0, stream>>>(
+        (long*)out, (const unsigned short*)logits, V);
 }
 
 }  // extern "C"

@@ -11,15 +11,17 @@
 #include <algorithm>
 
 extern "C" {
-void ps_rms_norm(void* out, const void* x, const void* w, float eps, long T,
-                 int D, hipStream_t stream);
-void ps_fused_add_rms_norm(void* x, void* residual, const void* w, float eps,
-                           long T, int D, hipStream_t stream);
-void ps_rms_norm_fp8(void* out_q, void* out_scale, void* x, void* residual,
-                     const void* w, float eps, long T, int D, int fused,
-                     hipStream_t stream);
-void ps_silu_and_mul_fp8(void* out_q, void* out_scale, const void* x, long T,
-                         int D, hipStream_t stream);
+// the row-in-registers launchers return non-zero, launching nothing, when D
+// is not a multiple of 8 or exceeds their largest instantiation
+int ps_rms_norm(void* out, const void* x, const void* w, float eps, long T,
+                int D, hipStream_t stream);
+int ps_fused_add_rms_norm(void* x, void* residual, const void* w, float eps,
+                          long T, int D, hipStream_t stream);
+int ps_rms_norm_fp8(void* out_q, void* out_scale, void* x, void* residual,
+                    const void* w, float eps, long T, int D, int fused,
+                    hipStream_t stream);
+int ps_silu_and_mul_fp8(void* out_q, void* out_scale, const void* x, long T,
+                        int D, hipStream_t stream);
 void ps_silu_and_mul(void* out, const void* x, long T, int D,
                      hipStream_t stream);
 void ps_rope(const void* positions, void* q, void* k, const void* cos_sin,
@@ -108,6 +110,30 @@ hipStream_t current_stream() {
   TORCH_CHECK((t).scalar_type() == (ty), #t " dtype mismatch"); \
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// [T] fp32 row scales and [T, D] fp8 codes written by the act-quant kernels
+void check_fp8_outputs(const at::Tensor& out_q, const at::Tensor& scales,
+                       long T, long D) {
+  TORCH_CHECK(out_q.is_cuda() && out_q.is_contiguous(),
+              "out_q must be GPU-contiguous");
+  TORCH_CHECK(out_q.scalar_type() == at::kFloat8_e4m3fn ||
+                  out_q.scalar_type() == at::kByte,
+              "out_q must be fp8/byte");
+  TORCH_CHECK(out_q.dim() == 2 && out_q.size(0) == T && out_q.size(1) == D,
+              "out_q must be [", T, ", ", D, "]");
+  CHECK_GPU_DTYPE(scales, at::kFloat);
+  TORCH_CHECK(scales.numel() == T, "scales must hold one value per row");
+}
+
+// rotary width taken from the cos/sin table: pairs (r, r + ROT/2) inside the
+// leading ROT dims of each head
+int rotary_dim(const at::Tensor& cos_sin, int HD) {
+  TORCH_CHECK(cos_sin.dim() == 2, "cos_sin must be [max_pos, rot_dim]");
+  const long ROT = cos_sin.size(1);
+  TORCH_CHECK(ROT >= 0 && ROT % 2 == 0, "rot_dim must be even, got ", ROT);
+  TORCH_CHECK(ROT <= HD, "rot_dim ", ROT, " exceeds head_dim ", HD);
+  return (int)ROT;
+}
+
 // KV caches are bf16 or OCP fp8 e4m3; returns 1 for fp8
 int cache_fp8(const at::Tensor& c) {
   TORCH_CHECK(c.is_cuda() && c.is_contiguous(), "cache must be GPU-contig");
@@ -130,11 +156,15 @@ void rms_norm(at::Tensor out, at::Tensor x, at::Tensor w, double eps) {
   CHECK_GPU_BF16(out);
   CHECK_GPU_BF16(x);
   CHECK_GPU_BF16(w);
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., D], D > 0");
   const long T = x.numel() / x.size(-1);
   const int D = (int)x.size(-1);
   TORCH_CHECK(D % 8 == 0, "hidden dim must be a multiple of 8");
-  ps_rms_norm(out.data_ptr(), x.data_ptr(), w.data_ptr(), (float)eps, T, D,
-              current_stream());
+  TORCH_CHECK(out.sizes() == x.sizes(), "out must have x's shape");
+  TORCH_CHECK(w.numel() == D, "w must hold D=", D, " weights");
+  int rc = ps_rms_norm(out.data_ptr(), x.data_ptr(), w.data_ptr(), (float)eps,
+                       T, D, current_stream());
+  TORCH_CHECK(rc == 0, "rms_norm: unsupported hidden dim ", D);
 }
 
 void fused_add_rms_norm(at::Tensor x, at::Tensor residual, at::Tensor w,
@@ -142,20 +172,27 @@ void fused_add_rms_norm(at::Tensor x, at::Tensor residual, at::Tensor w,
   CHECK_GPU_BF16(x);
   CHECK_GPU_BF16(residual);
   CHECK_GPU_BF16(w);
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, "x must be [..., D], D > 0");
   const long T = x.numel() / x.size(-1);
   const int D = (int)x.size(-1);
   TORCH_CHECK(D % 8 == 0, "hidden dim must be a multiple of 8");
-  ps_fused_add_rms_norm(x.data_ptr(), residual.data_ptr(), w.data_ptr(),
-                        (float)eps, T, D, current_stream());
+  TORCH_CHECK(residual.sizes() == x.sizes(), "residual must have x's shape");
+  TORCH_CHECK(w.numel() == D, "w must hold D=", D, " weights");
+  int rc = ps_fused_add_rms_norm(x.data_ptr(), residual.data_ptr(),
+                                 w.data_ptr(), (float)eps, T, D,
+                                 current_stream());
+  TORCH_CHECK(rc == 0, "fused_add_rms_norm: unsupported hidden dim ", D);
 }
 
 void silu_and_mul(at::Tensor out, at::Tensor x) {
   CHECK_GPU_BF16(out);
   CHECK_GPU_BF16(x);
+  TORCH_CHECK(out.dim() >= 1 && out.size(-1) > 0, "out must be [..., D]");
   const int D = (int)out.size(-1);
   TORCH_CHECK(x.size(-1) == 2 * D, "x last dim must be 2*out last dim");
   TORCH_CHECK(D % 8 == 0, "feature dim must be a multiple of 8");
   const long T = out.numel() / D;
+  TORCH_CHECK(x.numel() == 2 * T * D, "x must be [..., 2*D] over out's rows");
   ps_silu_and_mul(out.data_ptr(), x.data_ptr(), T, D, current_stream());
 }
 
@@ -165,9 +202,13 @@ void rotary_embedding(at::Tensor positions, at::Tensor q, at::Tensor k,
   CHECK_GPU_BF16(q);
   CHECK_GPU_BF16(k);
   CHECK_GPU_DTYPE(cos_sin, at::kFloat);
-  const long T = positions.size(0);
+  const long T = positions.numel();
+  TORCH_CHECK(head_dim > 0, "head_dim must be positive");
   const int HD = (int)head_dim;
-  const int ROT = (int)cos_sin.size(-1);
+  const int ROT = rotary_dim(cos_sin, HD);
+  if (T == 0) return;
+  TORCH_CHECK(q.numel() % (T * HD) == 0 && k.numel() % (T * HD) == 0,
+              "q/k must be [T, H*head_dim]");
   const int QH = (int)(q.numel() / T / HD);
   const int KH = (int)(k.numel() / T / HD);
   ps_rope(positions.data_ptr(), q.data_ptr(), k.data_ptr(),
@@ -322,14 +363,22 @@ void fused_rope_cache(at::Tensor qkv, at::Tensor positions,
   CHECK_GPU_DTYPE(slot_mapping, at::kLong);
   const int kv_fp8 = cache_fp8(k_cache);
   cache_fp8(v_cache);
-  const long T = positions.size(0);
+  const long T = positions.numel();
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                  v_cache.scalar_type() == k_cache.scalar_type(),
+              "k/v cache must both be [NB, KH, BS, HD] of one dtype");
   const int KH = (int)k_cache.size(1);
   const int BS = (int)k_cache.size(2);
+  TORCH_CHECK(head_dim > 0 && head_dim % 8 == 0,
+              "head_dim must be a positive multiple of 8");
   const int HD = (int)head_dim;
-  const int ROT = (int)cos_sin.size(-1);
-  TORCH_CHECK(
-      qkv.size(-1) == (q_heads + 2 * KH) * HD,
-      "qkv width mismatch");
+  TORCH_CHECK(k_cache.size(3) == HD, "cache head_dim mismatch");
+  const int ROT = rotary_dim(cos_sin, HD);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == T &&
+                  qkv.size(1) == (q_heads + 2 * KH) * HD,
+              "qkv must be [T, (q_heads + 2*KH) * head_dim]");
+  TORCH_CHECK(slot_mapping.numel() == T, "one slot per token");
+  if (T == 0) return;
   ps_fused_rope_cache(qkv.data_ptr(), positions.data_ptr(),
                       cos_sin.data_ptr(), slot_mapping.data_ptr(),
                       k_cache.data_ptr(), v_cache.data_ptr(), T,
@@ -344,11 +393,17 @@ void reshape_and_cache(at::Tensor k, at::Tensor v, at::Tensor k_cache,
   const int kv_fp8 = cache_fp8(k_cache);
   cache_fp8(v_cache);
   CHECK_GPU_DTYPE(slot_mapping, at::kLong);
-  const long T = slot_mapping.size(0);
+  const long T = slot_mapping.numel();
+  TORCH_CHECK(k_cache.dim() == 4 && v_cache.sizes() == k_cache.sizes() &&
+                  v_cache.scalar_type() == k_cache.scalar_type(),
+              "k/v cache must both be [NB, KH, BS, HD] of one dtype");
   const int KH = (int)k_cache.size(1);
   const int BS = (int)k_cache.size(2);
   const int HD = (int)k_cache.size(3);
+  TORCH_CHECK(HD % 8 == 0, "head_dim must be a multiple of 8");
   TORCH_CHECK(k.numel() == T * KH * HD, "k shape mismatch");
+  TORCH_CHECK(v.numel() == T * KH * HD, "v shape mismatch");
+  if (T == 0) return;
   ps_reshape_and_cache(k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
                        v_cache.data_ptr(), slot_mapping.data_ptr(), T, KH, HD,
                        BS, kv_fp8, current_stream());
@@ -384,24 +439,33 @@ void rms_norm_fp8(at::Tensor out_q, at::Tensor scales, at::Tensor x,
                   int64_t fused) {
   CHECK_GPU_BF16(x);
   CHECK_GPU_BF16(w);
-  CHECK_GPU_DTYPE(scales, at::kFloat);
-  TORCH_CHECK(out_q.scalar_type() == at::kFloat8_e4m3fn ||
-                  out_q.scalar_type() == at::kByte,
-              "out_q must be fp8/byte");
+  TORCH_CHECK(x.dim() == 2, "x must be [T, D]");
   const long T = x.size(0);
   const int D = (int)x.size(1);
-  ps_rms_norm_fp8(out_q.data_ptr(), scales.data_ptr(), x.data_ptr(),
-                  fused ? residual.data_ptr() : nullptr, w.data_ptr(),
-                  (float)eps, T, D, (int)fused, current_stream());
+  TORCH_CHECK(D % 8 == 0, "hidden dim must be a multiple of 8");
+  TORCH_CHECK(w.numel() == D, "w must hold D=", D, " weights");
+  check_fp8_outputs(out_q, scales, T, D);
+  if (fused) {
+    CHECK_GPU_BF16(residual);
+    TORCH_CHECK(residual.sizes() == x.sizes(), "residual must have x's shape");
+  }
+  int rc = ps_rms_norm_fp8(out_q.data_ptr(), scales.data_ptr(), x.data_ptr(),
+                           fused ? residual.data_ptr() : nullptr,
+                           w.data_ptr(), (float)eps, T, D, (int)fused,
+                           current_stream());
+  TORCH_CHECK(rc == 0, "rms_norm_fp8: unsupported hidden dim ", D);
 }
 
 void silu_and_mul_fp8(at::Tensor out_q, at::Tensor scales, at::Tensor x) {
   CHECK_GPU_BF16(x);
-  CHECK_GPU_DTYPE(scales, at::kFloat);
+  TORCH_CHECK(x.dim() == 2 && x.size(1) % 2 == 0, "x must be [T, 2*D]");
   const long T = x.size(0);
-  const int D = (int)x.size(1) / 2;
-  ps_silu_and_mul_fp8(out_q.data_ptr(), scales.data_ptr(), x.data_ptr(), T,
-                      D, current_stream());
+  const int D = (int)(x.size(1) / 2);
+  TORCH_CHECK(D % 8 == 0, "feature dim must be a multiple of 8");
+  check_fp8_outputs(out_q, scales, T, D);
+  int rc = ps_silu_and_mul_fp8(out_q.data_ptr(), scales.data_ptr(),
+                               x.data_ptr(), T, D, current_stream());
+  TORCH_CHECK(rc == 0, "silu_and_mul_fp8: unsupported feature dim ", D);
 }
 
 void gemm8p(at::Tensor out, at::Tensor x, at::Tensor w) {
@@ -430,8 +494,11 @@ void gemm8p(at::Tensor out, at::Tensor x, at::Tensor w) {
 
 void lora_bgmv(at::Tensor out, at::Tensor x, at::Tensor A, at::Tensor B,
                at::Tensor scale, at::Tensor idx, long col_off) {
-  CHECK_GPU_BF16(out);
-  CHECK_GPU_BF16(x);
+  // out and x may be row-strided views of wider buffers
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16,
+              "out must be bf16 on the GPU");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
+              "x must be bf16 on the GPU");
   CHECK_GPU_BF16(A);
   CHECK_GPU_BF16(B);
   CHECK_GPU_DTYPE(scale, at::kFloat);
@@ -447,12 +514,21 @@ void lora_bgmv(at::Tensor out, at::Tensor x, at::Tensor A, at::Tensor B,
   TORCH_CHECK(A.size(2) == IN, "A IN mismatch");
   TORCH_CHECK(B.size(2) == R, "B R mismatch");
   TORCH_CHECK(out.size(0) == T && idx.numel() == T, "T mismatch");
-  TORCH_CHECK(col_off + W <= out.size(1), "col range out of bounds");
+  TORCH_CHECK(col_off >= 0 && col_off + W <= out.size(1),
+              "col range out of bounds");
+  TORCH_CHECK(A.size(0) == B.size(0) && scale.numel() == A.size(0),
+              "A, B and scale must agree on the slot count");
+  TORCH_CHECK(IN % 8 == 0, "IN must be a multiple of 8, got ", IN);
+  TORCH_CHECK(x.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x rows must start on 16-byte boundaries");
+  TORCH_CHECK(R >= 1 && R <= 64, "lora_bgmv supports rank 1..64, got ", R);
+  if (T == 0) return;
   int rc = ps_lora_bgmv(out.data_ptr(), x.data_ptr(), A.data_ptr(),
                         B.data_ptr(), scale.data_ptr(), idx.data_ptr(), T,
                         IN, W, R, out.stride(0), x.stride(0), (int)col_off,
                         current_stream());
-  TORCH_CHECK(rc == 0, "lora_bgmv unsupported (R>64?) R=", R);
+  TORCH_CHECK(rc == 0, "lora_bgmv launch rejected: R=", R, " IN=", IN);
 }
 
 bool fused_moe_supported(int64_t T, int64_t top_k, int64_t E, int64_t H,
@@ -518,9 +594,13 @@ void kv_quant(at::Tensor out, at::Tensor scales, at::Tensor in) {
   CHECK_GPU_DTYPE(out, at::kChar);
   CHECK_GPU_DTYPE(scales, at::kFloat);
   CHECK_GPU_BF16(in);
+  TORCH_CHECK(in.dim() >= 1 && in.size(-1) > 0, "in must be [..., hd]");
   const int hd = (int)in.size(-1);
   TORCH_CHECK(hd % 8 == 0, "row width must be multiple of 8");
   const long rows = in.numel() / hd;
+  TORCH_CHECK(out.sizes() == in.sizes(), "out must have in's shape");
+  TORCH_CHECK(scales.numel() == rows, "scales must hold one value per row");
+  if (rows == 0) return;
   ps_kv_quant(out.data_ptr(), scales.data_ptr(), in.data_ptr(), rows, hd,
               current_stream());
 }
@@ -529,8 +609,13 @@ void kv_dequant(at::Tensor out, at::Tensor in, at::Tensor scales) {
   CHECK_GPU_BF16(out);
   CHECK_GPU_DTYPE(in, at::kChar);
   CHECK_GPU_DTYPE(scales, at::kFloat);
+  TORCH_CHECK(out.dim() >= 1 && out.size(-1) > 0, "out must be [..., hd]");
   const int hd = (int)out.size(-1);
+  TORCH_CHECK(hd % 8 == 0, "row width must be multiple of 8");
   const long rows = out.numel() / hd;
+  TORCH_CHECK(in.sizes() == out.sizes(), "in must have out's shape");
+  TORCH_CHECK(scales.numel() == rows, "scales must hold one value per row");
+  if (rows == 0) return;
   ps_kv_dequant(out.data_ptr(), in.data_ptr(), scales.data_ptr(), rows, hd,
                 current_stream());
 }
@@ -538,8 +623,12 @@ void kv_dequant(at::Tensor out, at::Tensor in, at::Tensor scales) {
 void greedy_sample(at::Tensor out, at::Tensor logits) {
   CHECK_GPU_DTYPE(out, at::kLong);
   CHECK_GPU_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0,
+              "logits must be [R, V], V > 0");
   const long R = logits.size(0);
   const int V = (int)logits.size(1);
+  TORCH_CHECK(out.numel() == R, "out must hold one index per row");
+  if (R == 0) return;
   ps_greedy_sample(out.data_ptr(), logits.data_ptr(), R, V, current_stream());
 }
 

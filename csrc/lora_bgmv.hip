@@ -71,7 +71,11 @@ int ps_lora_bgmv(void* out, const void* x, const void* A, const void* B,
                  const void* scale, const void* idx, int T, int IN, int W,
                  int R, long out_stride, long x_stride, int col_off,
                  hipStream_t stream) {
-  if (R > BGMV_RMAX || T == 0) return -1;
+  if (R < 1 || R > BGMV_RMAX || T <= 0 || W < 0) return -1;
+  // phase 1 reads x and A rows as 16-byte vectors of 8 bf16
+  if (IN <= 0 || IN % 8 != 0 || x_stride % 8 != 0 || (uintptr_t)x % 16 != 0 ||
+      (uintptr_t)A % 16 != 0)
+    return -2;
   bgmv_kernel<<<dim3(T), 256, 0, stream>>>(
       (unsigned short*)out, (const unsigned short*)x,
       (const unsigned short*)A, (const unsigned short*)B,

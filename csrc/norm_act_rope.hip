@@ -178,40 +178,49 @@ __global__ void rope_kernel(const int* __restrict__ positions,  // [T]
 // ---------------------------------------------------------------------------
 extern "C" {
 
-void ps_rms_norm(void* out, const void* x, const void* w, float eps, long T,
-                 int D, hipStream_t stream) {
-  constexpr int BLOCK = 256;
+// A row lives in vals[MAX_VPT][8] per thread, so an instantiation holds at
+// most BLOCK * 8 * MAX_VPT elements. Each launcher below takes the first
+// instantiation whose capacity covers D and returns non-zero, launching
+// nothing, when D is not a multiple of the 8-element vector or exceeds the
+// largest one.
+#define PS_ROW_CAPACITY(BLOCK, MAX_VPT) ((BLOCK) * 8 * (MAX_VPT))
+
+int ps_rms_norm(void* out, const void* x, const void* w, float eps, long T,
+                int D, hipStream_t stream) {
+  if (D <= 0 || D % 8 != 0) return -1;
+  if (T <= 0) return 0;
   dim3 grid((unsigned)T);
-  if (D <= BLOCK * 8 * 2)
-    rms_norm_kernel<BLOCK, 2><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)out, (const unsigned short*)x,
-        (const unsigned short*)w, eps, D);
-  else if (D <= BLOCK * 8 * 4)
-    rms_norm_kernel<BLOCK, 4><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)out, (const unsigned short*)x,
-        (const unsigned short*)w, eps, D);
-  else
-    rms_norm_kernel<BLOCK, 16><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)out, (const unsigned short*)x,
-        (const unsigned short*)w, eps, D);
+#define PS_RN(B, V)                                                 \
+  if (D <= PS_ROW_CAPACITY(B, V)) {                                 \
+    rms_norm_kernel<B, V><<<grid, B, 0, stream>>>(                  \
+        (unsigned short*)out, (const unsigned short*)x,             \
+        (const unsigned short*)w, eps, D);                          \
+    return 0;                                                       \
+  }
+  PS_RN(256, 2)
+  PS_RN(256, 4)
+  PS_RN(256, 16)
+#undef PS_RN
+  return -1;
 }
 
-void ps_fused_add_rms_norm(void* x, void* residual, const void* w, float eps,
-                           long T, int D, hipStream_t stream) {
-  constexpr int BLOCK = 256;
+int ps_fused_add_rms_norm(void* x, void* residual, const void* w, float eps,
+                          long T, int D, hipStream_t stream) {
+  if (D <= 0 || D % 8 != 0) return -1;
+  if (T <= 0) return 0;
   dim3 grid((unsigned)T);
-  if (D <= BLOCK * 8 * 2)
-    fused_add_rms_norm_kernel<BLOCK, 2><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)x, (unsigned short*)residual,
-        (const unsigned short*)w, eps, D);
-  else if (D <= BLOCK * 8 * 4)
-    fused_add_rms_norm_kernel<BLOCK, 4><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)x, (unsigned short*)residual,
-        (const unsigned short*)w, eps, D);
-  else
-    fused_add_rms_norm_kernel<BLOCK, 16><<<grid, BLOCK, 0, stream>>>(
-        (unsigned short*)x, (unsigned short*)residual,
-        (const unsigned short*)w, eps, D);
+#define PS_FARN(B, V)                                               \
+  if (D <= PS_ROW_CAPACITY(B, V)) {                                 \
+    fused_add_rms_norm_kernel<B, V><<<grid, B, 0, stream>>>(        \
+        (unsigned short*)x, (unsigned short*)residual,              \
+        (const unsigned short*)w, eps, D);                          \
+    return 0;                                                       \
+  }
+  PS_FARN(256, 2)
+  PS_FARN(256, 4)
+  PS_FARN(256, 16)
+#undef PS_FARN
+  return -1;
 }
 
 void ps_silu_and_mul(void* out, const void* x, long T, int D,
@@ -524,35 +533,46 @@ __global__ __launch_bounds__(BLOCK) void silu_and_mul_fp8_kernel(
 
 extern "C" {
 
-void ps_rms_norm_fp8(void* out_q, void* out_scale, void* x, void* residual,
-                     const void* w, float eps, long T, int D, int fused,
-                     hipStream_t stream) {
+int ps_rms_norm_fp8(void* out_q, void* out_scale, void* x, void* residual,
+                    const void* w, float eps, long T, int D, int fused,
+                    hipStream_t stream) {
+  if (D <= 0 || D % 8 != 0) return -1;
+  if (T <= 0) return 0;
   dim3 grid((unsigned)T);
-#define PS_RNF(B, V, F)                                                   \
-  rms_norm_fp8_kernel<B, V, F><<<grid, B, 0, stream>>>(                    \
-      (unsigned char*)out_q, (float*)out_scale, (unsigned short*)x,       \
-      (unsigned short*)residual, (const unsigned short*)w, eps, D)
-  if (fused) {
-    if (D <= 4096) PS_RNF(512, 1, true);
-    else PS_RNF(1024, 2, true);
-  } else {
-    if (D <= 4096) PS_RNF(512, 1, false);
-    else PS_RNF(1024, 2, false);
+#define PS_RNF(B, V)                                                      \
+  if (D <= PS_ROW_CAPACITY(B, V)) {                                       \
+    if (fused)                                                            \
+      rms_norm_fp8_kernel<B, V, true><<<grid, B, 0, stream>>>(            \
+          (unsigned char*)out_q, (float*)out_scale, (unsigned short*)x,   \
+          (unsigned short*)residual, (const unsigned short*)w, eps, D);   \
+    else                                                                  \
+      rms_norm_fp8_kernel<B, V, false><<<grid, B, 0, stream>>>(           \
+          (unsigned char*)out_q, (float*)out_scale, (unsigned short*)x,   \
+          (unsigned short*)residual, (const unsigned short*)w, eps, D);   \
+    return 0;                                                             \
   }
+  PS_RNF(512, 1)
+  PS_RNF(1024, 2)
 #undef PS_RNF
+  return -1;
 }
 
-void ps_silu_and_mul_fp8(void* out_q, void* out_scale, const void* x, long T,
-                         int D, hipStream_t stream) {
+int ps_silu_and_mul_fp8(void* out_q, void* out_scale, const void* x, long T,
+                        int D, hipStream_t stream) {
+  if (D <= 0 || D % 8 != 0) return -1;
+  if (T <= 0) return 0;
   dim3 grid((unsigned)T);
-  if (D <= 4096)
-    silu_and_mul_fp8_kernel<512, 1><<<grid, 512, 0, stream>>>(
-        (unsigned char*)out_q, (float*)out_scale,
-        (const unsigned short*)x, D);
-  else
-    silu_and_mul_fp8_kernel<1024, 4><<<grid, 1024, 0, stream>>>(
-        (unsigned char*)out_q, (float*)out_scale,
-        (const unsigned short*)x, D);
+#define PS_SMF(B, V)                                                  \
+  if (D <= PS_ROW_CAPACITY(B, V)) {                                   \
+    silu_and_mul_fp8_kernel<B, V><<<grid, B, 0, stream>>>(            \
+        (unsigned char*)out_q, (float*)out_scale,                     \
+        (const unsigned short*)x, D);                                 \
+    return 0;                                                         \
+  }
+  PS_SMF(512, 1)
+  PS_SMF(1024, 4)
+#undef PS_SMF
+  return -1;
 }
 
 }  // extern "C"

@@ -26,7 +26,11 @@ def fused_add_rms_norm(
     x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float
 ) -> tuple[torch.Tensor, torch.Tensor]:
     """Returns (normed, new_residual). Matches the in-place kernel: the
-    residual accumulator is stored in bf16 (summed in fp32, rounded once)."""
+    residual accumulator is stored in bf16 (summed in fp32, rounded once).
+
+    This reference norms the ROUNDED (bf16) sum, while the GPU kernels norm
+    the fp32 sum they still hold in registers and round only what they store;
+    the two differ by up to a bf16 rounding of the norm's input."""
     summed = (x.float() + residual.float()).to(x.dtype)
     return rms_norm(summed, w, eps), summed
 

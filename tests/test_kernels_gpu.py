@@ -9,6 +9,7 @@ import torch
 
 from production_stack_amd import ops
 from production_stack_amd.ops import reference
+from tests import elementwise_criteria as ec
 
 pytestmark = pytest.mark.gpu
 
@@ -331,10 +332,16 @@ def test_kv_quant_gpu_matches_reference():
     torch.testing.assert_close(
         s_gpu.cpu(), s_ref, atol=1e-5, rtol=1e-4
     )
-    # quantized codes may differ by 1 ulp at rounding boundaries
+    # codes are round-half-even of the fp64 quotient; only near-ties may
+    # differ by 1
+    ec.assert_int8_codes(q_gpu, s_gpu, x, "kv_quant")
     diff = (q_gpu.cpu().int() - q_ref.int()).abs()
     assert diff.max() <= 1
     y = ops.kv_dequant(q_gpu, s_gpu)
+    ec.assert_bits_equal(
+        y, (q_gpu.cpu().float() * s_gpu.cpu()[:, None]).to(torch.bfloat16),
+        "kv_dequant",
+    )
     torch.testing.assert_close(
         y.float().cpu(), x.float().cpu(), atol=0.05, rtol=0.05
     )
@@ -483,22 +490,19 @@ def test_engine_fp8_kv_e2e():
 
 
 def test_lora_bgmv_kernel_matches_reference():
-    from production_stack_amd import ops
-    from production_stack_amd.ops import reference
-
-    torch.manual_seed(1)
-    T, IN, W, R, S = 33, 1024, 768, 16, 4
-    x = torch.randn(T, IN, dtype=torch.bfloat16, device="cuda")
-    out = torch.randn(T, W + 32, dtype=torch.bfloat16, device="cuda")
-    A = (torch.randn(S, R, IN, dtype=torch.bfloat16, device="cuda") * 0.05)
-    B = (torch.randn(S, W, R, dtype=torch.bfloat16, device="cuda") * 0.05)
-    scale = torch.rand(S, device="cuda") + 0.5
-    idx = torch.randint(-1, S, (T,), dtype=torch.int32, device="cuda")
-    want = out.clone().cpu()
-    reference.lora_bgmv(want, x.cpu(), A.cpu(), B.cpu(), scale.cpu(),
-                        idx.cpu(), 16)
-    ops.lora_bgmv(out, x, A, B, scale, idx, col_off=16)
+    """T=33, IN=1024, W=768, R=16 at col_off 16: the touched block within one
+    bf16 rounding (plus the measured fp32 slack of this case) of the fp64
+    value, everything else untouched."""
+    d, slack = ec.lora_case("t33_in1024_w768_r16")
+    out = d["out"].cuda()
+    ops.lora_bgmv(out, d["x"].cuda(), d["A"].cuda(), d["B"].cuda(),
+                  d["scale"].cuda(), d["idx"].cuda(), col_off=d["col_off"])
     torch.cuda.synchronize()
+    ec.check_lora_bgmv(out, d["out"], d["x"], d["A"], d["B"], d["scale"],
+                       d["idx"], d["col_off"], slack, "lora_bgmv")
+    want = d["out"].clone()
+    reference.lora_bgmv(want, d["x"], d["A"], d["B"], d["scale"], d["idx"],
+                        d["col_off"])
     diff = (out.cpu().float() - want.float()).abs().max()
     assert diff < 0.25, f"max diff {diff}"
 
@@ -664,8 +668,9 @@ def test_prefill_mfma32_v5_windowed():
 
 
 def test_rms_norm_fp8_fused_act_quant():
-    """Fused (add-)RMSNorm -> fp8 + row scales vs the bf16 kernel output
-    (dequantized error bounded by fp8 e4m3 resolution)."""
+    """Fused (add-)RMSNorm -> fp8 + row scales: every code within one e4m3
+    rounding of the fp64 norm over the emitted scale, the scale amax/448,
+    and in the fused form the residual updated and x left alone."""
     torch.manual_seed(50)
     for fused in (False, True):
         T, D = 37, 4096
@@ -675,11 +680,18 @@ def test_rms_norm_fp8_fused_act_quant():
         if fused:
             x2, r2 = x.clone(), res.clone()
             want, r_want = ops.fused_add_rms_norm(x2, r2, w, 1e-5)
-            xq, sx = ops.rms_norm_fp8(x.clone(), w, 1e-5,
-                                      residual=res.clone())
+            x_in, r_io = x.clone(), res.clone()
+            xq, sx = ops.rms_norm_fp8(x_in, w, 1e-5, residual=r_io)
+            ec.assert_bits_equal(r_io, ec.residual_sum_bf16(x, res),
+                                 "new residual")
+            ec.assert_bits_equal(r_io, r_want, "residual vs bf16 kernel")
+            ec.assert_bits_equal(x_in, x, "x must stay as it was")
+            ref = ec.ref_rms_norm(x, w, 1e-5, residual=res)
         else:
             want = ops.rms_norm(x, w, 1e-5)
             xq, sx = ops.rms_norm_fp8(x, w, 1e-5)
+            ref = ec.ref_rms_norm(x, w, 1e-5)
+        ec.assert_fp8_rounded(xq, sx, ref, f"rms_norm_fp8 fused={fused}")
         got = xq.float() * sx[:, None]
         err = (got - want.float()).abs()
         # fp8 e4m3 has a 3-bit mantissa: ~6.25% relative resolution
@@ -693,6 +705,7 @@ def test_silu_and_mul_fp8():
     x = torch.randn(T, 2 * D, dtype=torch.bfloat16, device="cuda")
     want = ops.silu_and_mul(x)
     aq, sa = ops.silu_and_mul_fp8(x)
+    ec.assert_fp8_rounded(aq, sa, ec.ref_silu_and_mul(x), "silu_and_mul_fp8")
     got = aq.float() * sa[:, None]
     err = (got - want.float()).abs()
     tol = 0.08 * want.float().abs() + sa[:, None] * 2
