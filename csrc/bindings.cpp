@@ -76,6 +76,12 @@ void ps_kv_dequant(void* out, const void* in, const void* scales, long rows,
 int ps_skinny_gemm_splits(int M, int N, int K);
 int ps_skinny_gemm(void* out_bf16, void* ws, const void* x, const void* w,
                    int M, int N, int K, long x_stride, hipStream_t stream);
+int ps_skinny_gemm_fp8_splits(int M, int N, int K);
+int ps_skinny_gemm_fp8(void* out_bf16, void* ws, const void* xq,
+                       const void* sx, const void* wq, const void* sw, int M,
+                       int N, int K, hipStream_t stream);
+int ps_quant_fp8_rows(void* out_q, void* out_scale, const void* x, long T,
+                      int D, long x_stride, hipStream_t stream);
 int ps_gemm8p_splits(int M, int N, int K);
 int ps_gemm8p(void* out_bf16, void* ws, const void* x, const void* w, int M,
               int N, int K, long x_stride, hipStream_t stream);
@@ -468,6 +474,64 @@ void silu_and_mul_fp8(at::Tensor out_q, at::Tensor scales, at::Tensor x) {
   TORCH_CHECK(rc == 0, "silu_and_mul_fp8: unsupported feature dim ", D);
 }
 
+void quant_fp8_rows(at::Tensor out_q, at::Tensor scales, at::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
+              "x must be bf16 on the GPU");
+  TORCH_CHECK(x.dim() == 2 && (x.size(1) <= 1 || x.stride(1) == 1),
+              "x must be [T, D] with contiguous rows");
+  const long T = x.size(0);
+  const int D = (int)x.size(1);
+  TORCH_CHECK(D > 0 && D % 8 == 0, "feature dim must be a multiple of 8");
+  // rows are read as 16-byte vectors
+  TORCH_CHECK(T <= 1 || x.stride(0) % 8 == 0,
+              "x row stride must be a multiple of 8 elements");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0,
+              "x rows must be 16-byte aligned");
+  check_fp8_outputs(out_q, scales, T, D);
+  int rc = ps_quant_fp8_rows(out_q.data_ptr(), scales.data_ptr(),
+                             x.data_ptr(), T, D, T > 1 ? x.stride(0) : D,
+                             current_stream());
+  TORCH_CHECK(rc == 0, "quant_fp8_rows: unsupported feature dim ", D);
+}
+
+void skinny_gemm_fp8(at::Tensor out, at::Tensor xq, at::Tensor sx,
+                     at::Tensor wq, at::Tensor sw) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_DTYPE(xq, at::kFloat8_e4m3fn);
+  CHECK_GPU_DTYPE(wq, at::kFloat8_e4m3fn);
+  CHECK_GPU_DTYPE(sx, at::kFloat);
+  CHECK_GPU_DTYPE(sw, at::kFloat);
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2, "xq and wq must be 2D");
+  const int M = (int)xq.size(0);
+  const int K = (int)xq.size(1);
+  const int N = (int)wq.size(0);
+  TORCH_CHECK(xq.size(0) <= 256, "unsupported skinny fp8 gemm M=",
+              xq.size(0));
+  TORCH_CHECK(wq.size(1) == K, "K mismatch");
+  TORCH_CHECK(sx.numel() == M, "sx must hold one scale per row of xq");
+  TORCH_CHECK(sw.numel() == N, "sw must hold one scale per row of wq");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "out must be [", M, ", ", N, "]");
+  const int splits = ps_skinny_gemm_fp8_splits(M, N, K);
+  TORCH_CHECK(splits > 0, "unsupported skinny fp8 gemm shape M=", M, " N=", N,
+              " K=", K);
+  // rows are read as 16-byte vectors; K % 64 == 0 keeps every row start
+  // aligned once the base is
+  TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 &&
+                  (uintptr_t)wq.data_ptr() % 16 == 0,
+              "xq and wq rows must be 16-byte aligned");
+  void* ws_p = nullptr;
+  at::Tensor ws;
+  if (splits > 1) {
+    ws = at::empty({(long)splits * M * N}, sx.options());
+    ws_p = ws.data_ptr();
+  }
+  int rc = ps_skinny_gemm_fp8(out.data_ptr(), ws_p, xq.data_ptr(),
+                              sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), M,
+                              N, K, current_stream());
+  TORCH_CHECK(rc == 0, "skinny fp8 gemm launch failed");
+}
+
 void gemm8p(at::Tensor out, at::Tensor x, at::Tensor w) {
   CHECK_GPU_BF16(out);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
@@ -683,6 +747,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Split-K depth gemm8p picks for (M, N, K); -1 if unsupported");
   m.def("skinny_gemm_splits", &ps_skinny_gemm_splits,
         "Split-K depth skinny_gemm picks for (M, N, K); -1 if unsupported");
+  m.def("skinny_gemm_fp8", &skinny_gemm_fp8,
+        "fp8 e4m3 split-K MFMA GEMM with row/channel scales (M<=256)");
+  m.def("skinny_gemm_fp8_splits", &ps_skinny_gemm_fp8_splits,
+        "Split-K depth skinny_gemm_fp8 picks for (M, N, K); -1 if "
+        "unsupported");
+  m.def("quant_fp8_rows", &quant_fp8_rows,
+        "Per-row fp8 quantization of a (row-strided) bf16 matrix");
   m.def("kv_dequant", &kv_dequant, "Row-wise int8 KV dequantization");
   m.def("fused_moe", &fused_moe,
         "Grouped MoE expert MLP (align + gate_up/SiLU + down + combine)");

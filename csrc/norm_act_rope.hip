@@ -531,7 +531,75 @@ __global__ __launch_bounds__(BLOCK) void silu_and_mul_fp8_kernel(
   }
 }
 
+// Plain per-row quantizer for activations no fused producer can emit as fp8
+// (the attention output in front of the o-projection). x may be a
+// row-strided view; same scale rule as the fused kernels above.
+template <int BLOCK, int MAX_VPT>
+__global__ __launch_bounds__(BLOCK) void quant_fp8_rows_kernel(
+    unsigned char* __restrict__ out_q,     // [T, D] fp8
+    float* __restrict__ out_scale,         // [T]
+    const unsigned short* __restrict__ x,  // [T, D], row stride x_stride
+    int D, long x_stride) {
+  const long t = blockIdx.x;
+  const unsigned short* xr = x + t * x_stride;
+  unsigned char* orow = out_q + t * (long)D;
+
+  float vals[MAX_VPT][8];
+  int nvec = 0;
+  float amax = 1e-6f;
+  for (int i = threadIdx.x * 8; i < D; i += BLOCK * 8) {
+    ps_bf16x8 xv = *(const ps_bf16x8*)(xr + i);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      float f = ps_bf16_to_f32(xv[j]);
+      vals[nvec][j] = f;
+      amax = fmaxf(amax, fabsf(f));
+    }
+    nvec++;
+  }
+  __shared__ float reda[BLOCK / 64];
+  amax = ps_group_max<64>(amax);
+  if ((threadIdx.x & 63) == 0) reda[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float m = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < BLOCK / 64; wv++) m = fmaxf(m, reda[wv]);
+    reda[0] = m / 448.0f;
+    out_scale[t] = m / 448.0f;
+  }
+  __syncthreads();
+  const float rs = 1.0f / reda[0];
+  nvec = 0;
+  for (int i = threadIdx.x * 8; i < D; i += BLOCK * 8) {
+    ps_fp8x8 qv;
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      qv[j] = ps_f32_to_fp8(vals[nvec][j] * rs);
+    *(ps_fp8x8*)(orow + i) = qv;
+    nvec++;
+  }
+}
+
 extern "C" {
+
+int ps_quant_fp8_rows(void* out_q, void* out_scale, const void* x, long T,
+                      int D, long x_stride, hipStream_t stream) {
+  if (D <= 0 || D % 8 != 0) return -1;
+  if (T <= 0) return 0;
+  dim3 grid((unsigned)T);
+#define PS_QFR(B, V)                                                  \
+  if (D <= PS_ROW_CAPACITY(B, V)) {                                   \
+    quant_fp8_rows_kernel<B, V><<<grid, B, 0, stream>>>(              \
+        (unsigned char*)out_q, (float*)out_scale,                     \
+        (const unsigned short*)x, D, x_stride);                       \
+    return 0;                                                         \
+  }
+  PS_QFR(512, 1)
+  PS_QFR(1024, 4)
+#undef PS_QFR
+  return -1;
+}
 
 int ps_rms_norm_fp8(void* out_q, void* out_scale, void* x, void* residual,
                     const void* w, float eps, long T, int D, int fused,

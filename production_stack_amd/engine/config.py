@@ -385,6 +385,11 @@ class EngineConfig:
     # weight quantization: None (bf16) or "fp8" (OCP e4m3 weights +
     # dynamic per-tensor activation quant through the fp8 MFMA pipe)
     quantization: Optional[str] = None
+    # fp8 GEMM backend, read only when quantization == "fp8": "scaled_mm"
+    # (torch._scaled_mm / hipBLASLt) or "native" (csrc/skinny_gemm_fp8.hip
+    # with per-row activation and per-channel weight scales for steps of up
+    # to 256 tokens; larger steps fall through to _scaled_mm)
+    fp8_gemm: str = "scaled_mm"
     # sparse-MoE expert dispatch: "loop" (per-expert Python loop over
     # hipBLASLt GEMMs; host syncs, so no decode hipGraphs) or "fused"
     # (csrc/moe_fused.hip grouped kernels for steps with T*top_k <= 1024;

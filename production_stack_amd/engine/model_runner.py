@@ -81,7 +81,14 @@ class ModelRunner:
             self.model.lora_slots = self.lora_slots
             for layer in self.model.layers:
                 layer.lora_slots = self.lora_slots
+        if config.fp8_gemm not in ("scaled_mm", "native"):
+            raise ValueError(
+                f"unknown fp8_gemm {config.fp8_gemm!r}; "
+                "expected 'scaled_mm' or 'native'"
+            )
         if config.quantization == "fp8":
+            for layer in self.model.layers:
+                layer.fp8_gemm = config.fp8_gemm
             self.model.quantize_fp8()
         if config.moe_backend not in ("loop", "fused"):
             raise ValueError(
@@ -187,7 +194,8 @@ class ModelRunner:
         from production_stack_amd.engine.graph_runner import DecodeGraphRunner
         from production_stack_amd.ops import gemm_policy
 
-        # fp8-quantized GEMMs run through scaled_mm: nothing to autotune
+        # fp8-quantized GEMMs run through scaled_mm or the native fp8
+        # kernel (config.fp8_gemm): nothing to autotune
         if self.config.quantization != "fp8":
             try:
                 layer0 = self.model.layers[0]

@@ -178,9 +178,14 @@ class LlamaLayer(nn.Module):
         # directly, skipping the bf16 round trip;
         # LoRA needs the bf16 normed activations, so it keeps the plain
         # norm + per-tensor fp8 GEMM path.
+        # fp8_gemm == "native" runs the rowwise GEMMs in
+        # csrc/skinny_gemm_fp8.hip, so it takes this path whether or not
+        # _scaled_mm accepts rowwise scales.
+        backend = getattr(self, "fp8_gemm", "scaled_mm")
         fuse_q = (fp8 is not None and hidden.is_cuda
                   and meta.lora_idx is None and not meta.lora_groups
-                  and ops.fp8_rowwise_supported(hidden.device))
+                  and (backend == "native"
+                       or ops.fp8_rowwise_supported(hidden.device)))
         if fuse_q:
             if residual is None:
                 residual = hidden.clone()
@@ -190,7 +195,8 @@ class LlamaLayer(nn.Module):
                 xq, sx = ops.rms_norm_fp8(
                     hidden, self.input_norm, cfg.rms_norm_eps,
                     residual=residual)
-            qkv = ops.fp8_linear_rowwise(xq, sx, *fp8["qkv"])
+            qkv = ops.fp8_linear_rowwise(xq, sx, *fp8["qkv"],
+                                         backend=backend)
         else:
             if residual is None:
                 residual = hidden
@@ -313,7 +319,12 @@ class LlamaLayer(nn.Module):
             attn = buf
         else:
             attn = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
-        if getattr(self, "fp8_w", None) is not None:
+        if fuse_q and backend == "native":
+            # nothing upstream can emit the attention output quantized
+            aq, sa = ops.quant_fp8_rows(attn.view(T, qs))
+            attn_out = ops.fp8_linear_rowwise(aq, sa, *fp8["o"],
+                                              backend=backend)
+        elif fp8 is not None:
             attn_out = ops.fp8_linear(attn.reshape(T, qs),
                                       *self.fp8_w["o"])
         else:
@@ -340,7 +351,8 @@ class LlamaLayer(nn.Module):
                 attn_out, self.post_attn_norm, cfg.rms_norm_eps,
                 residual=residual)
             hidden = attn_out  # bf16 normed not materialized on this path
-            gate_up = ops.fp8_linear_rowwise(xq, sx, *fp8["gate_up"])
+            gate_up = ops.fp8_linear_rowwise(xq, sx, *fp8["gate_up"],
+                                             backend=backend)
         else:
             hidden, residual = ops.fused_add_rms_norm(
                 attn_out, residual, self.post_attn_norm, cfg.rms_norm_eps
@@ -366,7 +378,8 @@ class LlamaLayer(nn.Module):
         if fuse_q:
             aq, sa = ops.silu_and_mul_fp8(gate_up)
             act = gate_up[:, : self.inter]  # only LoRA reads act; unused
-            mlp_out = ops.fp8_linear_rowwise(aq, sa, *fp8["down"])
+            mlp_out = ops.fp8_linear_rowwise(aq, sa, *fp8["down"],
+                                             backend=backend)
         else:
             act = ops.silu_and_mul(gate_up)
             if fp8 is not None:
@@ -488,7 +501,9 @@ class LlamaForCausalLM(nn.Module):
         per-output-channel scales (vLLM --quantization fp8 analogue);
         halves
         weight HBM and runs GEMMs through the fp8 MFMA pipe. Embedding,
-        lm_head and norms stay bf16."""
+        lm_head and norms stay bf16. Scales are per output channel when
+        the layer's fp8_gemm is "native" or _scaled_mm takes rowwise
+        scales, per tensor otherwise."""
         for layer in self.layers:
             fp8_w = {}
             proj_names = [("qkv", "qkv_proj"), ("o", "o_proj")]
@@ -497,8 +512,9 @@ class LlamaForCausalLM(nn.Module):
                                ("down", "down_proj")]
             for key, pname in proj_names:
                 w = getattr(layer, pname)
-                if (w.is_cuda
-                        and ops.fp8_rowwise_supported(w.device)):
+                if (getattr(layer, "fp8_gemm", "scaled_mm") == "native"
+                        or (w.is_cuda
+                            and ops.fp8_rowwise_supported(w.device))):
                     w_q, scale = ops.fp8_quantize_weight_rowwise(w.data)
                 else:
                     w_q, scale = ops.fp8_quantize_weight(w.data)

@@ -1237,6 +1237,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--quantization", default=None,
                     choices=[None, "fp8"],
                     help="fp8 = OCP e4m3 weights through the fp8 MFMA pipe")
+    ap.add_argument("--fp8-gemm", default="scaled_mm",
+                    choices=["scaled_mm", "native"],
+                    help="with --quantization fp8: native = hand-written "
+                         "fp8 MFMA GEMM with row/channel scales for steps "
+                         "of up to 256 tokens")
     ap.add_argument("--moe-backend", default="loop",
                     choices=["loop", "fused"],
                     help="fused = grouped MoE expert kernels + decode "
@@ -1310,6 +1315,7 @@ def main() -> None:
         speculative_model=args.speculative_model,
         speculative_weights_path=args.speculative_weights_path,
         quantization=args.quantization,
+        fp8_gemm=args.fp8_gemm,
         moe_backend=args.moe_backend,
         enable_lora=args.enable_lora,
         max_loras=args.max_loras,

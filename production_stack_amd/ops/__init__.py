@@ -507,11 +507,68 @@ def fp8_rowwise_supported(device="cuda") -> bool:
     return _ROWWISE_SCALED_MM
 
 
-def fp8_linear_rowwise(xq, sx, w_q, sw):
+def skinny_gemm_fp8_supported(M: int, N: int, K: int) -> bool:
+    """The accept rule of csrc/skinny_gemm_fp8.hip
+    (ps_skinny_gemm_fp8_splits > 0): decode-sized M, 64-aligned N and K."""
+    return (
+        1 <= M <= 256 and N >= 64 and K >= 64
+        and N % 64 == 0 and K % 64 == 0
+    )
+
+
+def skinny_gemm_fp8(xq, sx, wq, sw) -> torch.Tensor:
+    """out[M,N] bf16 = (xq*sx[:,None]) @ (wq*sw[:,None]).T with xq [M,K]
+    and wq [N,K] OCP e4m3, sx [M] and sw [N] fp32, through the hand-written
+    fp8 MFMA kernel (csrc/skinny_gemm_fp8.hip): fp32 accumulation, scales
+    applied once before the bf16 round, bit-deterministic, and a row's
+    result does not depend on M. GPU only; shapes outside
+    skinny_gemm_fp8_supported raise. M == 0 returns an empty [0, N]."""
+    _require_ext()
+    out = torch.empty(
+        (xq.shape[0], wq.shape[0]), dtype=torch.bfloat16, device=xq.device
+    )
+    if xq.shape[0] == 0:
+        return out
+    _C.skinny_gemm_fp8(out, xq, sx, wq, sw)
+    return out
+
+
+def quant_fp8_rows(x: torch.Tensor):
+    """Per-row dynamic fp8 quantization of a bf16 [T, D] matrix (rows may
+    be strided): returns (xq e4m3 [T, D], sx fp32 [T]) with
+    sx = max(row amax, 1e-6) / 448, the rule of the fused act-quant
+    kernels. x is left unchanged."""
+    if x.is_cuda:
+        _require_ext()
+        T, D = x.shape
+        out_q = torch.empty((T, D), dtype=torch.float8_e4m3fn,
+                            device=x.device)
+        scales = torch.empty(T, dtype=torch.float32, device=x.device)
+        _C.quant_fp8_rows(out_q, scales, x)
+        return out_q, scales
+    return reference.quant_fp8_rows(x)
+
+
+def fp8_linear_rowwise(xq, sx, w_q, sw, backend="scaled_mm"):
     """out[M,N] = (xq*sx[:,None]) @ (w_q*sw[None,:]).T in fp8 tensor
     cores with per-row activation + per-channel weight scales. Uses
     _scaled_mm's rowwise scaling when this build supports it, else a
-    unit-scale fp8 GEMM with the outer-product scale applied after."""
+    unit-scale fp8 GEMM with the outer-product scale applied after.
+
+    backend="native" runs skinny_gemm_fp8 instead when the input is on the
+    GPU and skinny_gemm_fp8_supported(M, N, K) holds. Everything else
+    (prefill chunks with M > 256, shard shapes that are not 64-aligned)
+    falls through to the _scaled_mm path above, unchanged."""
+    if backend not in ("scaled_mm", "native"):
+        raise ValueError(
+            f"unknown fp8 gemm backend {backend!r}; "
+            "expected 'scaled_mm' or 'native'"
+        )
+    if (
+        backend == "native" and xq.is_cuda
+        and skinny_gemm_fp8_supported(xq.shape[0], w_q.shape[0], xq.shape[1])
+    ):
+        return skinny_gemm_fp8(xq, sx, w_q, sw)
     if fp8_rowwise_supported(xq.device):
         return torch._scaled_mm(
             xq, w_q.t(), scale_a=sx[:, None].contiguous(),

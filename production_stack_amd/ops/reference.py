@@ -192,6 +192,23 @@ def kv_dequant(q: torch.Tensor, scales: torch.Tensor,
     return rows.to(dtype).view(q.shape)
 
 
+def quant_fp8_rows(x: torch.Tensor) -> tuple:
+    """Per-row fp8-e4m3 quantization of [T, D]: scale = max(row amax, 1e-6)
+    / 448 (the act-quant kernels' rule). Returns (codes e4m3, scales f32)."""
+    xf = x.float()
+    scales = xf.abs().amax(dim=-1).clamp(min=1e-6) / 448.0
+    q = (xf / scales[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn)
+    return q, scales
+
+
+def fp8_linear_rowwise(xq, sx, w_q, sw) -> torch.Tensor:
+    """out[M, N] bf16 = (xq * sx[:, None]) @ (w_q * sw[:, None]).T as an
+    fp32 dequantized matmul: the oracle for the fp8 GEMM kernels."""
+    xf = xq.float() * sx.float()[:, None]
+    wf = w_q.float() * sw.float()[:, None]
+    return (xf @ wf.t()).to(torch.bfloat16)
+
+
 def lora_bgmv(out, x, A, B, scale, idx, col_off):
     """Reference BGMV: out[t, col_off:+W] += scale[s] * B[s] @ (A[s] @ x[t])
     for s = idx[t] >= 0."""

@@ -36,6 +36,7 @@ ext = CUDAExtension(
         "csrc/prefill_mfma.hip",
         "csrc/prefill_mfma32.hip",
         "csrc/skinny_gemm.hip",
+        "csrc/skinny_gemm_fp8.hip",
         "csrc/gemm8p.hip",
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
