@@ -9,6 +9,9 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <vector>
+
+#include "step_pack.h"
 
 extern "C" {
 // the row-in-registers launchers return non-zero, launching nothing, when D
@@ -95,6 +98,9 @@ int ps_fused_moe(void* out, void* offsets, void* sorted_pairs, void* act,
                  const void* w_down, const void* topk_ids, int ids_i64,
                  const void* topk_w, int T, int top_k, int E, int H, int I,
                  hipStream_t stream);
+int ps_resolve_placeholders(void* tokens, const void* prev_row,
+                            const void* prev_tokens, long n, long n_prev,
+                            hipStream_t stream);
 }
 
 at::Tensor cachegen_encode(at::Tensor q);
@@ -696,6 +702,101 @@ void greedy_sample(at::Tensor out, at::Tensor logits) {
   ps_greedy_sample(out.data_ptr(), logits.data_ptr(), R, V, current_stream());
 }
 
+void resolve_placeholders(at::Tensor tokens, at::Tensor prev_row,
+                          at::Tensor prev_tokens) {
+  CHECK_GPU_DTYPE(tokens, at::kLong);
+  CHECK_GPU_DTYPE(prev_row, at::kInt);
+  CHECK_GPU_DTYPE(prev_tokens, at::kLong);
+  TORCH_CHECK(tokens.dim() == 1 && prev_row.dim() == 1 &&
+                  prev_tokens.dim() == 1,
+              "resolve_placeholders takes 1-D tensors");
+  TORCH_CHECK(prev_row.numel() == tokens.numel(),
+              "prev_row must hold one entry per token row");
+  if (tokens.numel() == 0) return;
+  int rc = ps_resolve_placeholders(tokens.data_ptr(), prev_row.data_ptr(),
+                                   prev_tokens.data_ptr(), tokens.numel(),
+                                   prev_tokens.numel(), current_stream());
+  TORCH_CHECK(rc == 0, "resolve_placeholders launch rejected");
+}
+
+// Python-list front end of ps::step_pack (csrc/step_pack.h). `desc` holds
+// five ints per sequence: start, num_tokens, is_decode, sample_last,
+// prev_row. `tables` is the list of the sequences' block tables as they are.
+// Returns (status, layout fields...) in StepPackLayout order.
+py::tuple pack_step_inputs(at::Tensor buf, py::list desc, py::list token_ids,
+                           py::list tables, int64_t block_size,
+                           int64_t tile_rows) {
+  TORCH_CHECK(buf.device().is_cpu() && buf.scalar_type() == at::kByte &&
+                  buf.dim() == 1 && buf.is_contiguous(),
+              "buf must be a contiguous 1-D uint8 host tensor");
+  TORCH_CHECK(block_size > 0 && block_size <= INT32_MAX && tile_rows > 0 &&
+                  tile_rows <= INT32_MAX,
+              "bad block_size / tile_rows");
+  const int64_t n = (int64_t)tables.size();
+  TORCH_CHECK((int64_t)desc.size() == 5 * n,
+              "desc must hold 5 ints per sequence");
+  auto as_long = [](PyObject* o) -> long {
+    long v = PyLong_AsLong(o);
+    if (v == -1 && PyErr_Occurred()) throw py::error_already_set();
+    return v;
+  };
+  auto as_i32 = [&](PyObject* o) -> int32_t {
+    long v = as_long(o);
+    TORCH_CHECK(v >= INT32_MIN && v <= INT32_MAX, "value exceeds int32");
+    return (int32_t)v;
+  };
+  std::vector<int32_t> start(n), count(n), prev(n);
+  std::vector<uint8_t> dec(n), samp(n);
+  std::vector<int64_t> table_off(n + 1, 0);
+  for (int64_t s = 0; s < n; ++s) {
+    PyObject* d = desc.ptr();
+    start[s] = as_i32(PyList_GET_ITEM(d, 5 * s));
+    count[s] = as_i32(PyList_GET_ITEM(d, 5 * s + 1));
+    dec[s] = as_long(PyList_GET_ITEM(d, 5 * s + 2)) != 0;
+    samp[s] = as_long(PyList_GET_ITEM(d, 5 * s + 3)) != 0;
+    prev[s] = as_i32(PyList_GET_ITEM(d, 5 * s + 4));
+    PyObject* t = PyList_GET_ITEM(tables.ptr(), s);
+    TORCH_CHECK(PyList_Check(t), "each block table must be a list");
+    table_off[s + 1] = table_off[s] + (int64_t)PyList_GET_SIZE(t);
+  }
+  std::vector<int32_t> flat(table_off[n]);
+  for (int64_t s = 0; s < n; ++s) {
+    PyObject* t = PyList_GET_ITEM(tables.ptr(), s);
+    int32_t* dst = flat.data() + table_off[s];
+    const Py_ssize_t len = PyList_GET_SIZE(t);
+    for (Py_ssize_t j = 0; j < len; ++j) {
+      dst[j] = as_i32(PyList_GET_ITEM(t, j));
+    }
+  }
+  const int64_t nt = (int64_t)token_ids.size();
+  std::vector<int64_t> ids(nt);
+  for (int64_t j = 0; j < nt; ++j) {
+    ids[j] = as_long(PyList_GET_ITEM(token_ids.ptr(), j));
+  }
+  ps::StepPackIn in;
+  in.num_seqs = n;
+  in.start = start.data();
+  in.num_tokens = count.data();
+  in.is_decode = dec.data();
+  in.sample_last = samp.data();
+  in.prev_row = prev.data();
+  in.token_ids = ids.data();
+  in.num_token_ids = nt;
+  in.tables = flat.data();
+  in.num_table_entries = (int64_t)flat.size();
+  in.table_off = table_off.data();
+  in.block_size = (int32_t)block_size;
+  in.tile_rows = (int32_t)tile_rows;
+  ps::StepPackLayout layout;
+  const int status =
+      ps::step_pack(in, buf.data_ptr(), buf.numel(), &layout);
+  py::tuple out(1 + ps::kStepPackFields);
+  out[0] = status;
+  const int64_t* f = reinterpret_cast<const int64_t*>(&layout);
+  for (int64_t i = 0; i < ps::kStepPackFields; ++i) out[1 + i] = f[i];
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -730,6 +831,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reshape_and_cache", &reshape_and_cache,
         "Append K/V for new tokens into the paged cache");
   m.def("greedy_sample", &greedy_sample, "Per-row argmax over vocab");
+  m.def("resolve_placeholders", &resolve_placeholders,
+        "tokens[i] = prev_tokens[prev_row[i]] where prev_row[i] >= 0");
+  m.def("pack_step_inputs", &pack_step_inputs,
+        "Pack one step's inputs into a host buffer (csrc/step_pack.h)");
   m.def("kv_quant", &kv_quant, "Row-wise int8 KV quantization");
   m.def("rms_norm_fp8", &rms_norm_fp8,
         "RMSNorm (optionally fused residual add) emitting fp8 + row scales");

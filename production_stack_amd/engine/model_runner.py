@@ -8,6 +8,7 @@ chunk), multi-token chunks through the chunked-prefill kernel.
 
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -116,6 +117,14 @@ class ModelRunner:
         self._prev_rows: Dict[str, int] = {}
         self._async_host = [None, None]
         self._async_host_i = 0
+        # native step-input path (prepare_native): two pinned staging
+        # buffers + device arenas used alternately, each with the event of
+        # its last upload. PS_NATIVE_PREPARE=0 forces prepare() for A/B.
+        self.native_prepare = (
+            os.environ.get("PS_NATIVE_PREPARE", "1") != "0"
+        )
+        self._stage = [None, None]
+        self._stage_i = 0
 
     # ------------------------------------------------------------------
     @property
@@ -431,6 +440,187 @@ class ModelRunner:
         return token_t, meta, sample_seqs, rows_t
 
     # ------------------------------------------------------------------
+    def native_prepare_covers(self, out: SchedulerOutput) -> bool:
+        """What prepare_native handles: single-GPU serving on a CUDA device
+        without LoRA, multimodal embeds or draft tokens in the step.
+        Everything else goes through prepare()."""
+        if (
+            not self.native_prepare
+            or not ops.HAVE_EXT
+            or self.device.type != "cuda"
+            or self.pipeline is not None
+            or self.tp_coord is not None
+            or getattr(self, "tp_serving", False)
+            or self.lora_slots is not None
+            or not out.scheduled
+        ):
+            return False
+        for ss in out.scheduled:
+            seq = ss.seq
+            if ss.draft_tokens or seq.lora_name:
+                return False
+            if not ss.is_decode and getattr(seq, "mm_embeds", None):
+                return False
+        return True
+
+    def _stage_buffers(self, nbytes: int, advance: bool = True):
+        """The next (host staging, device arena) pair (the current one
+        again if not `advance`), at least nbytes large. The host side is
+        safe to overwrite on return: the upload that last read it has
+        completed."""
+        if advance:
+            self._stage_i ^= 1
+        st = self._stage[self._stage_i]
+        if st is not None and st["event"] is not None:
+            # recorded two prepares ago; long complete in steady state
+            st["event"].synchronize()
+            st["event"] = None
+        if st is None or st["host"].numel() < nbytes:
+            cap = max(2 * nbytes, 1 << 16)
+            cuda = self.device.type == "cuda"
+            st = {
+                "host": torch.empty(cap, dtype=torch.uint8, pin_memory=cuda),
+                "dev": torch.empty(cap, dtype=torch.uint8,
+                                   device=self.device),
+                "event": None,
+            }
+            self._stage[self._stage_i] = st
+        return st
+
+    def prepare_native(self, out: SchedulerOutput, bm: BlockManager):
+        """prepare() for the steps native_prepare_covers accepts: the host
+        arrays are packed in C++ (csrc/step_pack.h) into one pinned buffer
+        and uploaded with ONE copy; the returned tensors are typed views of
+        the device arena. No host read of device data, no pageable copy.
+
+        Returns (token_t, meta, sample_seqs, rows_t, prev_row_t, n_ph):
+        prev_row_t holds, per token row, the row of the previous step's
+        sampled tensor an async placeholder takes its token from (-1 for
+        real tokens) and n_ph counts such rows (resolve with
+        ops.resolve_placeholders before the forward). Returns None when a
+        placeholder cannot be resolved on the device (one inside a prefill
+        chunk, or a decode row unknown to the previous step): the sync path
+        must run."""
+        prefills = [s for s in out.scheduled if not s.is_decode]
+        decodes = [s for s in out.scheduled if s.is_decode]
+        desc: List[int] = []
+        tokens: List[int] = []
+        tables: List[List[int]] = []
+        sample_seqs: List[Sequence] = []
+        for ss in prefills:
+            seq = ss.seq
+            start = seq.num_computed
+            end = start + ss.num_tokens
+            if end <= seq.num_prompt:
+                tokens.extend(seq.prompt_token_ids[start:end])
+            else:
+                tokens.extend(seq.token_ids()[start:end])
+            sampled = end == seq.num_tokens
+            if sampled:
+                sample_seqs.append(seq)
+            desc.extend((start, ss.num_tokens, 0, int(sampled), -1))
+            tables.append(seq.block_table)
+        prev_rows = self._prev_rows
+        for ss in decodes:
+            seq = ss.seq
+            pos = seq.num_computed
+            npr = seq.num_prompt
+            tok = (seq.prompt_token_ids[pos] if pos < npr
+                   else seq.output_token_ids[pos - npr])
+            row = -1
+            if tok < 0:
+                row = prev_rows.get(seq.request_id, -1)
+                if self._prev_tokens_dev is None:
+                    return None
+            tokens.append(tok)
+            desc.extend((pos, 1, 1, 1, row))
+            tables.append(seq.block_table)
+            sample_seqs.append(seq)
+        TILE = ops.prefill_tile_rows(
+            self.model_cfg.num_q_heads, self.model_cfg.num_kv_heads
+        )
+        # the pack is retried once into a larger buffer when it does not fit
+        need = 0
+        for attempt in range(2):
+            st = self._stage_buffers(need, advance=attempt == 0)
+            status, lay = ops.pack_step_inputs(
+                st["host"], desc, tokens, tables, bm.block_size, TILE
+            )
+            if status != ops.PACK_TOO_SMALL:
+                break
+            need = lay["total_bytes"]
+        if status in (ops.PACK_PREFILL_PLACEHOLDER,
+                      ops.PACK_DECODE_UNRESOLVED):
+            return None
+        if status != ops.PACK_OK:
+            raise RuntimeError(f"pack_step_inputs failed: status {status}")
+        n = lay["total_bytes"]
+        arena = st["dev"]
+        arena[:n].copy_(st["host"][:n], non_blocking=True)
+        if self.device.type == "cuda":
+            st["event"] = torch.cuda.Event()
+            st["event"].record()
+
+        def view(off: str, count: int, dtype, elem: int):
+            if count == 0:
+                return None
+            o = lay[off]
+            return arena[o:o + count * elem].view(dtype)
+
+        i32, i64 = torch.int32, torch.int64
+        T = lay["num_tokens"]
+        Tp = lay["num_prefill_tokens"]
+        Sp, Sd = lay["num_prefill_seqs"], lay["num_decode_seqs"]
+        mb = lay["max_bt"]
+        empty = arena[:0]
+        token_t = view("off_tokens", T, i64, 8)
+        rows_t = view("off_sample_rows", lay["num_sample_rows"], i64, 8)
+        tiles = view("off_prefill_tiles", lay["num_tiles"] * 4, i32, 4)
+        p_bt = view("off_prefill_block_tables", Sp * mb, i32, 4)
+        d_bt = view("off_decode_block_tables", Sd * mb, i32, 4)
+        if Sp and p_bt is None:  # zero-width tables
+            p_bt = empty.view(i32)
+        if Sd and d_bt is None:
+            d_bt = empty.view(i32)
+        meta = BatchMeta(
+            positions=(view("off_positions", T, i32, 4)
+                       if T else empty.view(i32)),
+            slot_mapping=(view("off_slot_mapping", T, i64, 8)
+                          if T else empty.view(i64)),
+            num_prefill_tokens=Tp,
+            prefill_token_seq=view("off_prefill_token_seq", Tp, i32, 4),
+            prefill_token_pos=view("off_prefill_token_pos", Tp, i32, 4),
+            prefill_block_tables=(
+                p_bt.view(Sp, mb) if p_bt is not None else None),
+            num_decode_seqs=Sd,
+            decode_seq_lens=view("off_decode_seq_lens", Sd, i32, 4),
+            decode_block_tables=(
+                d_bt.view(Sd, mb) if d_bt is not None else None),
+            prefill_tiles=tiles.view(-1, 4) if tiles is not None else None,
+        )
+        return (
+            token_t if token_t is not None else empty.view(i64),
+            meta,
+            sample_seqs,
+            rows_t if rows_t is not None else empty.view(i64),
+            view("off_prev_row", T, i32, 4),
+            lay["num_placeholders"],
+        )
+
+    def _prepare_step(self, out: SchedulerOutput, bm: BlockManager):
+        """prepare() for the sync path: natively where covered."""
+        if self.native_prepare_covers(out):
+            got = self.prepare_native(out, bm)
+            if got is not None:
+                token_t, meta, sample_seqs, rows_t, prev_row_t, n_ph = got
+                if n_ph:
+                    ops.resolve_placeholders(
+                        token_t, prev_row_t, self._prev_tokens_dev
+                    )
+                return token_t, meta, sample_seqs, rows_t
+        return self.prepare(out, bm)
+
+    # ------------------------------------------------------------------
     @torch.no_grad()
     def _execute_decode_graph(
         self, out: SchedulerOutput, bm: BlockManager, defer_sample=False
@@ -534,7 +724,7 @@ class ModelRunner:
                     # pipeline on the stream (host profile showed two
                     # serialized GPU waits per mixed step without this)
                     logits_d, seqs_d = got
-                    token_t, meta, sample_seqs, rows_t = self.prepare(
+                    token_t, meta, sample_seqs, rows_t = self._prepare_step(
                         SchedulerOutput(scheduled=pre), bm
                     )
                     logits_p = None
@@ -563,7 +753,7 @@ class ModelRunner:
                             out_p, sample_seqs, toks_p, logits_p,
                         ))
                     return result
-        token_t, meta, sample_seqs, rows_t = self.prepare(out, bm)
+        token_t, meta, sample_seqs, rows_t = self._prepare_step(out, bm)
         if token_t.numel() == 0:
             return {}
         if self.pipeline is not None:
@@ -672,8 +862,25 @@ class ModelRunner:
         logits_p, seqs_p = None, []
         if eager:
             sub = SchedulerOutput(scheduled=list(eager))
-            token_t, meta, seqs_p, rows_t = self.prepare(sub, bm)
-            if token_t.numel():
+            native = self.native_prepare_covers(sub)
+            if native:
+                # one pinned upload, placeholders resolved on the device:
+                # nothing here waits for the previous step
+                got = self.prepare_native(sub, bm)
+                if got is None:
+                    return None
+                token_t, meta, seqs_p, rows_t, prev_row_t, n_ph = got
+                if token_t.numel():
+                    if n_ph:
+                        ops.resolve_placeholders(
+                            token_t, prev_row_t, self._prev_tokens_dev
+                        )
+                    hidden = self.model(token_t, meta, self.kv_caches)
+                    if seqs_p:
+                        logits_p = self.model.compute_logits(hidden[rows_t])
+            else:
+                token_t, meta, seqs_p, rows_t = self.prepare(sub, bm)
+            if not native and token_t.numel():
                 # resolve -1 placeholders (decode rows sit after the
                 # prefill-chunk rows) from the prev step's device tokens
                 prefill_rows = sum(

@@ -283,6 +283,57 @@ def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
     return reference.greedy_sample(logits)
 
 
+def resolve_placeholders(
+    tokens: torch.Tensor, prev_row: torch.Tensor, prev_tokens: torch.Tensor
+) -> torch.Tensor:
+    """In place: tokens[i] = prev_tokens[prev_row[i]] where prev_row[i] >= 0
+    (async scheduling: rows whose input token the previous step is still
+    sampling). tokens/prev_tokens int64, prev_row int32, one per row."""
+    if tokens.is_cuda:
+        _require_ext()
+        _C.resolve_placeholders(tokens, prev_row, prev_tokens)
+        return tokens
+    return reference.resolve_placeholders(tokens, prev_row, prev_tokens)
+
+
+# status codes of pack_step_inputs (csrc/step_pack.h)
+PACK_OK = 0
+PACK_TOO_SMALL = 1
+PACK_PREFILL_PLACEHOLDER = 2
+PACK_DECODE_UNRESOLVED = 3
+PACK_BAD_INPUT = 4
+
+# StepPackLayout fields, in order, after the status
+PACK_FIELDS = (
+    "total_bytes", "num_tokens", "num_prefill_tokens", "num_prefill_seqs",
+    "num_decode_seqs", "num_tiles", "max_bt", "num_sample_rows",
+    "num_placeholders", "off_tokens", "off_positions", "off_slot_mapping",
+    "off_prefill_token_seq", "off_prefill_token_pos", "off_prefill_tiles",
+    "off_prefill_block_tables", "off_decode_block_tables",
+    "off_decode_seq_lens", "off_sample_rows", "off_prev_row",
+)
+
+
+def pack_step_inputs(
+    buf: torch.Tensor,
+    desc: list,
+    token_ids: list,
+    tables: list,
+    block_size: int,
+    tile_rows: int,
+) -> tuple:
+    """Pack one step's inputs into the uint8 host tensor `buf` (host-only
+    C++, csrc/step_pack.h). `desc` holds five ints per sequence (start,
+    num_tokens, is_decode, sample_last, prev_row), `token_ids` the chunks'
+    ids back to back, `tables` the block tables as they are. Returns
+    (status, layout dict); nothing is written unless status is PACK_OK."""
+    _require_ext()
+    res = _C.pack_step_inputs(
+        buf, desc, token_ids, tables, block_size, tile_rows
+    )
+    return res[0], dict(zip(PACK_FIELDS, res[1:]))
+
+
 def kv_quant(x: torch.Tensor) -> tuple:
     """Row-wise int8 KV quantization (CacheGen-style serde)."""
     if x.is_cuda:

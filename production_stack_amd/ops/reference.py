@@ -173,6 +173,14 @@ def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
     return logits.float().argmax(dim=-1)
 
 
+def resolve_placeholders(
+    tokens: torch.Tensor, prev_row: torch.Tensor, prev_tokens: torch.Tensor
+) -> torch.Tensor:
+    ph = (prev_row >= 0).nonzero().flatten()
+    tokens[ph] = prev_tokens[prev_row[ph].long()]
+    return tokens
+
+
 def kv_quant(x: torch.Tensor) -> tuple:
     """Row-wise int8 quantization over the last dim. Returns (int8, scales)."""
     hd = x.shape[-1]

@@ -41,6 +41,7 @@ ext = CUDAExtension(
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
         "csrc/moe_fused.hip",
+        "csrc/step_inputs.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
