@@ -83,6 +83,13 @@ int ps_skinny_gemm_fp8_splits(int M, int N, int K);
 int ps_skinny_gemm_fp8(void* out_bf16, void* ws, const void* xq,
                        const void* sx, const void* wq, const void* sw, int M,
                        int N, int K, hipStream_t stream);
+int ps_skinny_gemm_w4_splits(int M, int N, int K);
+int ps_skinny_gemm_w4(void* out_bf16, void* ws, const void* x,
+                      const void* packed, const void* scales,
+                      const void* zeros, int M, int N, int K,
+                      hipStream_t stream);
+int ps_int4_dequant(void* out_bf16, const void* packed, const void* scales,
+                    const void* zeros, long N, int K, hipStream_t stream);
 int ps_quant_fp8_rows(void* out_q, void* out_scale, const void* x, long T,
                       int D, long x_stride, hipStream_t stream);
 int ps_gemm8p_splits(int M, int N, int K);
@@ -538,6 +545,82 @@ void skinny_gemm_fp8(at::Tensor out, at::Tensor xq, at::Tensor sx,
   TORCH_CHECK(rc == 0, "skinny fp8 gemm launch failed");
 }
 
+// packed [N, K/2] uint8, s [N, K/128] bf16, z [N, K/128] uint8 of one int4
+// weight; returns (N, K)
+std::pair<long, long> check_int4_weight(const at::Tensor& packed,
+                                        const at::Tensor& s,
+                                        const at::Tensor& z) {
+  CHECK_GPU_DTYPE(packed, at::kByte);
+  CHECK_GPU_BF16(s);
+  CHECK_GPU_DTYPE(z, at::kByte);
+  TORCH_CHECK(packed.dim() == 2, "packed must be [N, K/2]");
+  const long N = packed.size(0);
+  const long K = packed.size(1) * 2;
+  TORCH_CHECK(K >= 128 && K % 128 == 0,
+              "K must be a multiple of the int4 group size 128, got ", K);
+  TORCH_CHECK(s.dim() == 2 && s.size(0) == N && s.size(1) == K / 128,
+              "s must be [", N, ", ", K / 128, "]");
+  TORCH_CHECK(z.dim() == 2 && z.size(0) == N && z.size(1) == K / 128,
+              "z must be [", N, ", ", K / 128, "]");
+  TORCH_CHECK(packed.device() == s.device() && packed.device() == z.device(),
+              "packed, s and z must be on one device");
+  // rows are read as 16-byte vectors; K % 128 == 0 keeps every row start
+  // aligned once the base is
+  TORCH_CHECK((uintptr_t)packed.data_ptr() % 16 == 0,
+              "packed rows must be 16-byte aligned");
+  return {N, K};
+}
+
+void skinny_gemm_w4(at::Tensor out, at::Tensor x, at::Tensor packed,
+                    at::Tensor s, at::Tensor z) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_BF16(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
+  const auto nk = check_int4_weight(packed, s, z);
+  const int M = (int)x.size(0);
+  const int N = (int)nk.first;
+  const int K = (int)nk.second;
+  TORCH_CHECK(x.size(0) <= 256, "unsupported skinny w4 gemm M=", x.size(0));
+  TORCH_CHECK(x.size(1) == K, "K mismatch");
+  TORCH_CHECK(x.device() == packed.device() && out.device() == x.device(),
+              "out, x and the weight must be on one device");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "out must be [", M, ", ", N, "]");
+  const int splits = ps_skinny_gemm_w4_splits(M, N, K);
+  TORCH_CHECK(splits > 0, "unsupported skinny w4 gemm shape M=", M, " N=", N,
+              " K=", K);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0,
+              "x rows must be 16-byte aligned");
+  void* ws_p = nullptr;
+  at::Tensor ws;
+  if (splits > 1) {
+    ws = at::empty({(long)splits * M * N}, x.options().dtype(at::kFloat));
+    ws_p = ws.data_ptr();
+  }
+  int rc = ps_skinny_gemm_w4(out.data_ptr(), ws_p, x.data_ptr(),
+                             packed.data_ptr(), s.data_ptr(), z.data_ptr(),
+                             M, N, K, current_stream());
+  TORCH_CHECK(rc == 0, "skinny w4 gemm launch failed");
+}
+
+void int4_dequant(at::Tensor out, at::Tensor packed, at::Tensor s,
+                  at::Tensor z) {
+  CHECK_GPU_BF16(out);
+  const auto nk = check_int4_weight(packed, s, z);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == nk.first &&
+                  out.size(1) == nk.second,
+              "out must be [", nk.first, ", ", nk.second, "]");
+  TORCH_CHECK(out.device() == packed.device(),
+              "out and the weight must be on one device");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 16 == 0,
+              "out rows must be 16-byte aligned");
+  if (nk.first == 0) return;
+  int rc = ps_int4_dequant(out.data_ptr(), packed.data_ptr(), s.data_ptr(),
+                           z.data_ptr(), nk.first, (int)nk.second,
+                           current_stream());
+  TORCH_CHECK(rc == 0, "int4_dequant: unsupported shape");
+}
+
 void gemm8p(at::Tensor out, at::Tensor x, at::Tensor w) {
   CHECK_GPU_BF16(out);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
@@ -857,6 +940,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8_splits", &ps_skinny_gemm_fp8_splits,
         "Split-K depth skinny_gemm_fp8 picks for (M, N, K); -1 if "
         "unsupported");
+  m.def("skinny_gemm_w4", &skinny_gemm_w4,
+        "int4 weight-only (group 128) split-K MFMA GEMM, bf16 activations "
+        "(M<=256)");
+  m.def("skinny_gemm_w4_splits", &ps_skinny_gemm_w4_splits,
+        "Split-K depth skinny_gemm_w4 picks for (M, N, K); -1 if "
+        "unsupported");
+  m.def("int4_dequant", &int4_dequant,
+        "Packed int4 + group scales/zero points -> bf16 [N, K]");
   m.def("quant_fp8_rows", &quant_fp8_rows,
         "Per-row fp8 quantization of a (row-strided) bf16 matrix");
   m.def("kv_dequant", &kv_dequant, "Row-wise int8 KV dequantization");

@@ -382,8 +382,10 @@ class EngineConfig:
     # non-greedy sampling, penalties, logprobs or speculative chunks fall
     # back to the synchronous path transparently.
     async_scheduling: bool = False
-    # weight quantization: None (bf16) or "fp8" (OCP e4m3 weights +
-    # dynamic per-tensor activation quant through the fp8 MFMA pipe)
+    # weight quantization: None (bf16), "fp8" (OCP e4m3 weights +
+    # dynamic per-tensor activation quant through the fp8 MFMA pipe) or
+    # "int4" (weight-only, group 128, bf16 scales + zero points; bf16
+    # activations, so LoRA works). Anything else raises at engine start.
     quantization: Optional[str] = None
     # fp8 GEMM backend, read only when quantization == "fp8": "scaled_mm"
     # (torch._scaled_mm / hipBLASLt) or "native" (csrc/skinny_gemm_fp8.hip

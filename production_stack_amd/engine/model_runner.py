@@ -87,6 +87,13 @@ class ModelRunner:
                 f"unknown fp8_gemm {config.fp8_gemm!r}; "
                 "expected 'scaled_mm' or 'native'"
             )
+        if config.quantization not in (None, "fp8", "int4"):
+            raise ValueError(
+                f"unknown quantization {config.quantization!r}; "
+                "expected None, 'fp8' or 'int4'"
+            )
+        if config.quantization == "int4":
+            self.model.quantize_int4()
         if config.quantization == "fp8":
             for layer in self.model.layers:
                 layer.fp8_gemm = config.fp8_gemm
@@ -204,8 +211,9 @@ class ModelRunner:
         from production_stack_amd.ops import gemm_policy
 
         # fp8-quantized GEMMs run through scaled_mm or the native fp8
-        # kernel (config.fp8_gemm): nothing to autotune
-        if self.config.quantization != "fp8":
+        # kernel (config.fp8_gemm), int4 ones through the native int4
+        # kernel; the bf16 weights are gone: nothing to autotune
+        if self.config.quantization not in ("fp8", "int4"):
             try:
                 layer0 = self.model.layers[0]
                 weights = [layer0.qkv_proj, layer0.o_proj]

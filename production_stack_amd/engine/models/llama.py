@@ -16,6 +16,7 @@ sharded across the TP group; o_proj and down_proj outputs are all-reduced
 
 from __future__ import annotations
 
+import logging
 import math
 from typing import List, Optional
 
@@ -28,6 +29,7 @@ from production_stack_amd.ops import gemm_policy
 from production_stack_amd.engine.config import ModelConfig
 from production_stack_amd.parallel import state as pstate
 
+logger = logging.getLogger("engine.models.llama")
 
 class BatchMeta:
     """Per-step metadata consumed by the attention layers."""
@@ -174,6 +176,9 @@ class LlamaLayer(nn.Module):
     ) -> tuple:
         cfg = self.cfg
         fp8 = getattr(self, "fp8_w", None)
+        # int4 weight-only projections (quantize_int4): activations stay
+        # bf16, so only the four GEMM calls below change
+        int4 = getattr(self, "int4_w", None) or {}
         # fused act-quant path: (add-)RMSNorm emits fp8 + row scales
         # directly, skipping the bf16 round trip;
         # LoRA needs the bf16 normed activations, so it keeps the plain
@@ -208,6 +213,8 @@ class LlamaLayer(nn.Module):
                 )
             if fp8 is not None:
                 qkv = ops.fp8_linear(hidden, *fp8["qkv"])
+            elif "qkv" in int4:
+                qkv = ops.int4_linear(hidden, *int4["qkv"])
             else:
                 qkv = gemm_policy.linear(hidden, self.qkv_proj)
         if self.qkv_bias is not None:
@@ -327,6 +334,8 @@ class LlamaLayer(nn.Module):
         elif fp8 is not None:
             attn_out = ops.fp8_linear(attn.reshape(T, qs),
                                       *self.fp8_w["o"])
+        elif "o" in int4:
+            attn_out = ops.int4_linear(attn.reshape(T, qs), *int4["o"])
         else:
             attn_out = gemm_policy.linear(attn.view(T, qs), self.o_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -359,6 +368,8 @@ class LlamaLayer(nn.Module):
             )
             if fp8 is not None:
                 gate_up = ops.fp8_linear(hidden, *fp8["gate_up"])
+            elif "gate_up" in int4:
+                gate_up = ops.int4_linear(hidden, *int4["gate_up"])
             else:
                 gate_up = gemm_policy.linear(hidden, self.gate_up_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -384,6 +395,8 @@ class LlamaLayer(nn.Module):
             act = ops.silu_and_mul(gate_up)
             if fp8 is not None:
                 mlp_out = ops.fp8_linear(act, *fp8["down"])
+            elif "down" in int4:
+                mlp_out = ops.int4_linear(act, *int4["down"])
             else:
                 mlp_out = gemm_policy.linear(act, self.down_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -524,6 +537,37 @@ class LlamaForCausalLM(nn.Module):
                 w.data = torch.empty(0, dtype=torch.bfloat16,
                                      device=w.device)
             layer.fp8_w = fp8_w
+
+    @torch.no_grad()
+    def quantize_int4(self) -> None:
+        """Convert the four per-layer projections to int4 weight-only
+        (group 128 along K, bf16 scales, uint8 zero points; the AWQ/GPTQ
+        "W4A16" class). Activations stay bf16, so norms, RoPE, attention
+        and both LoRA paths run unchanged. A projection whose local shape
+        the int4 GEMM does not take (N % 64 or K % 128 non-zero, odd TP
+        shards) stays bf16. MoE experts, embedding, lm_head and norms stay
+        bf16, as for fp8."""
+        for layer in self.layers:
+            int4_w = {}
+            proj_names = [("qkv", "qkv_proj"), ("o", "o_proj")]
+            if not layer.n_experts:
+                proj_names += [("gate_up", "gate_up_proj"),
+                               ("down", "down_proj")]
+            for key, pname in proj_names:
+                w = getattr(layer, pname)
+                N, K = w.shape
+                if N % 64 or K % ops.INT4_GROUP:
+                    logger.warning(
+                        "layer %d %s [%d, %d] is not int4-quantizable "
+                        "(needs N %% 64 == 0 and K %% %d == 0); kept bf16",
+                        layer.layer_idx, pname, N, K, ops.INT4_GROUP,
+                    )
+                    continue
+                int4_w[key] = ops.int4_quantize_weight(w.data)
+                # free the bf16 copy, as quantize_fp8 does
+                w.data = torch.empty(0, dtype=torch.bfloat16,
+                                     device=w.device)
+            layer.int4_w = int4_w
 
     @property
     def kv_heads(self) -> int:

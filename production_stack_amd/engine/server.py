@@ -1235,8 +1235,10 @@ def build_arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv-cache-dtype", default="auto",
                     choices=["auto", "bf16", "fp8", "fp8_e4m3"])
     ap.add_argument("--quantization", default=None,
-                    choices=[None, "fp8"],
-                    help="fp8 = OCP e4m3 weights through the fp8 MFMA pipe")
+                    choices=[None, "fp8", "int4"],
+                    help="fp8 = OCP e4m3 weights through the fp8 MFMA pipe; "
+                         "int4 = weight-only 4-bit (group 128, W4A16), "
+                         "bf16 activations, works with LoRA")
     ap.add_argument("--fp8-gemm", default="scaled_mm",
                     choices=["scaled_mm", "native"],
                     help="with --quantization fp8: native = hand-written "

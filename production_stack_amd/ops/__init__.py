@@ -629,3 +629,77 @@ def fp8_linear_rowwise(xq, sx, w_q, sw, backend="scaled_mm"):
     out = torch._scaled_mm(xq, w_q.t(), scale_a=one, scale_b=one,
                            out_dtype=torch.float32)
     return (out * sx[:, None] * sw[None, :]).to(torch.bfloat16)
+
+
+# ---- int4 weight-only quantization (W4A16, group 128) ----
+# W_deq[n, k] = bf16_rne(float(q[n, k] - z[n, k/128]) * float(s[n, k/128]));
+# every path multiplies x by these bf16 values with fp32 accumulation.
+
+INT4_GROUP = reference.INT4_GROUP
+
+# The nibble order belongs to csrc/skinny_gemm_w4.hip; these two and the
+# kernels are the only code that knows it. Both take CPU and GPU tensors.
+int4_pack = reference.int4_pack
+int4_unpack = reference.int4_unpack
+
+
+def int4_quantize_weight(w: torch.Tensor):
+    """Round-to-nearest asymmetric int4 of w [N, K] with one bf16 scale and
+    one zero point per 128 k of a row: (packed uint8 [N, K/2], s bf16
+    [N, K/128], z uint8 [N, K/128]), on w's device."""
+    return reference.int4_quantize_weight(w)
+
+
+def int4_dequant(packed, s, z) -> torch.Tensor:
+    """packed + s + z -> W_deq [N, K] bf16 (csrc/skinny_gemm_w4.hip on the
+    GPU, the reference formula on the CPU)."""
+    if packed.is_cuda:
+        _require_ext()
+        out = torch.empty(
+            (packed.shape[0], packed.shape[1] * 2), dtype=torch.bfloat16,
+            device=packed.device,
+        )
+        _C.int4_dequant(out, packed, s, z)
+        return out
+    return reference.int4_dequant(packed, s, z)
+
+
+def skinny_gemm_w4_supported(M: int, N: int, K: int) -> bool:
+    """The accept rule of csrc/skinny_gemm_w4.hip
+    (ps_skinny_gemm_w4_splits > 0): decode-sized M, 64-aligned N, K in whole
+    128-wide quantization groups."""
+    return (
+        1 <= M <= 256 and N >= 64 and K >= INT4_GROUP
+        and N % 64 == 0 and K % INT4_GROUP == 0
+    )
+
+
+def skinny_gemm_w4(x, packed, s, z) -> torch.Tensor:
+    """out[M,N] bf16 = x[M,K] bf16 @ W_deq[N,K]^T through the hand-written
+    int4 MFMA kernel (csrc/skinny_gemm_w4.hip): weights dequantized in
+    registers to the bf16 values of int4_dequant, fp32 accumulation,
+    bit-deterministic, and a row's result does not depend on M. GPU only;
+    shapes outside skinny_gemm_w4_supported raise. M == 0 returns an empty
+    [0, N]."""
+    _require_ext()
+    out = torch.empty(
+        (x.shape[0], packed.shape[0]), dtype=torch.bfloat16, device=x.device
+    )
+    if x.shape[0] == 0:
+        return out
+    _C.skinny_gemm_w4(out, x, packed, s, z)
+    return out
+
+
+def int4_linear(x, packed, s, z) -> torch.Tensor:
+    """x @ W_deq^T for an int4 weight: the native kernel when x is on the
+    GPU and skinny_gemm_w4_supported(M, N, K) holds; otherwise (prefill
+    chunks with M > 256) int4_dequant into a transient bf16 buffer and the
+    bf16 GEMM dispatch; the reference on the CPU."""
+    if not x.is_cuda:
+        return reference.int4_linear(x, packed, s, z)
+    if skinny_gemm_w4_supported(x.shape[0], packed.shape[0], x.shape[1]):
+        return skinny_gemm_w4(x, packed, s, z)
+    from production_stack_amd.ops import gemm_policy
+
+    return gemm_policy.linear(x, int4_dequant(packed, s, z))

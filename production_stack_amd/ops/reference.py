@@ -217,6 +217,71 @@ def fp8_linear_rowwise(xq, sx, w_q, sw) -> torch.Tensor:
     return (xf @ wf.t()).to(torch.bfloat16)
 
 
+INT4_GROUP = 128  # k per (scale, zero point) of an int4 weight row
+
+
+def int4_pack(q: torch.Tensor) -> torch.Tensor:
+    """Logical q [N, K] (integers 0..15) -> packed uint8 [N, K/2] in the
+    layout csrc/skinny_gemm_w4.hip reads: k = 128c + 32j + 8g + i sits in
+    nibble i of the little-endian dword at byte 64c + 16g + 4j of the row."""
+    N, K = q.shape
+    if K % INT4_GROUP:
+        raise ValueError(f"K={K} is not a multiple of {INT4_GROUP}")
+    v = q.to(torch.uint8).reshape(N, K // INT4_GROUP, 4, 4, 8)  # c, j, g, i
+    v = v.permute(0, 1, 3, 2, 4)  # c, g, j, i
+    return (v[..., 0::2] | (v[..., 1::2] << 4)).reshape(N, K // 2)
+
+
+def int4_unpack(packed: torch.Tensor) -> torch.Tensor:
+    """Inverse of int4_pack: packed uint8 [N, K/2] -> q uint8 [N, K]."""
+    N, half = packed.shape
+    K = half * 2
+    if K % INT4_GROUP:
+        raise ValueError(f"K={K} is not a multiple of {INT4_GROUP}")
+    b = packed.reshape(N, K // INT4_GROUP, 4, 4, 4)  # c, g, j, byte
+    v = torch.stack([b & 0xF, b >> 4], dim=-1)  # c, g, j, byte, nibble
+    return v.view(N, K // INT4_GROUP, 4, 4, 8).permute(
+        0, 1, 3, 2, 4).reshape(N, K)
+
+
+def int4_quantize_weight(w: torch.Tensor) -> tuple:
+    """Round-to-nearest asymmetric int4 with one bf16 scale and one zero
+    point per 128 k of a row. Returns (packed uint8 [N, K/2], s bf16
+    [N, K/128], z uint8 [N, K/128]). The zero point and the codes are
+    computed with the stored (bf16-rounded) scale."""
+    N, K = w.shape
+    if K % INT4_GROUP:
+        raise ValueError(f"K={K} is not a multiple of {INT4_GROUP}")
+    g = w.float().view(N, K // INT4_GROUP, INT4_GROUP)
+    lo = g.amin(dim=-1).clamp(max=0.0)
+    hi = g.amax(dim=-1).clamp(min=0.0)
+    s = ((hi - lo).clamp(min=1e-5) / 15.0).to(torch.bfloat16)
+    sf = s.float()
+    z = torch.round(-lo / sf).clamp(0, 15)
+    q = (torch.round(g / sf[..., None]) + z[..., None]).clamp(0, 15)
+    return (
+        int4_pack(q.to(torch.uint8).view(N, K)), s, z.to(torch.uint8)
+    )
+
+
+def int4_dequant(packed: torch.Tensor, s: torch.Tensor,
+                 z: torch.Tensor) -> torch.Tensor:
+    """W_deq[n, k] = bf16_rne(float(q[n, k] - z[n, k/128]) * float(s[n,
+    k/128])); the fp32 product is exact, the bf16 round is the only one."""
+    q = int4_unpack(packed).float()
+    zf = z.float().repeat_interleave(INT4_GROUP, dim=1)
+    sf = s.float().repeat_interleave(INT4_GROUP, dim=1)
+    return ((q - zf) * sf).to(torch.bfloat16)
+
+
+def int4_linear(x, packed, s, z) -> torch.Tensor:
+    """out[M, N] bf16 = x @ W_deq^T with the bf16 W_deq of int4_dequant as
+    the operand and fp32 accumulation: the oracle for the int4 GEMM."""
+    wd = int4_dequant(packed, s, z)
+    return torch.nn.functional.linear(x.float(), wd.float()).to(
+        torch.bfloat16)
+
+
 def lora_bgmv(out, x, A, B, scale, idx, col_off):
     """Reference BGMV: out[t, col_off:+W] += scale[s] * B[s] @ (A[s] @ x[t])
     for s = idx[t] >= 0."""

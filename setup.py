@@ -37,6 +37,7 @@ ext = CUDAExtension(
         "csrc/prefill_mfma32.hip",
         "csrc/skinny_gemm.hip",
         "csrc/skinny_gemm_fp8.hip",
+        "csrc/skinny_gemm_w4.hip",
         "csrc/gemm8p.hip",
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
