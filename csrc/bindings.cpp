@@ -296,6 +296,27 @@ bool decode_order(at::Tensor order, at::Tensor seq_lens) {
                          (int)seq_lens.numel(), current_stream()) == 0;
 }
 
+// Host checks shared by the two prefill bindings (no device read): q is
+// [T, QH, hd] bf16 with contiguous heads (rows may be strided), out is
+// [T, QH, hd], K and V agree and carry hd, window is not negative.
+void check_prefill_args(const at::Tensor& out, const at::Tensor& q,
+                        const at::Tensor& k_cache, const at::Tensor& v_cache,
+                        const at::Tensor& block_tables, int64_t window) {
+  TORCH_CHECK(q.dim() == 3, "q must be [T, QH, head_dim]");
+  q_row_stride(q, (int)q.size(2));
+  TORCH_CHECK(out.sizes() == q.sizes(), "out must be [T, QH, head_dim]");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() &&
+                  k_cache.scalar_type() == v_cache.scalar_type(),
+              "k_cache and v_cache must be [NB, KH, BS, head_dim] of one "
+              "shape and dtype");
+  TORCH_CHECK(k_cache.size(3) == q.size(2),
+              "cache head_dim ", k_cache.size(3), " != q head_dim ",
+              q.size(2));
+  TORCH_CHECK(block_tables.dim() == 2,
+              "block_tables must be [num_seqs, max_blocks]");
+  TORCH_CHECK(window >= 0, "window must be >= 0, got ", window);
+}
+
 void paged_attn_prefill(at::Tensor out, at::Tensor q, at::Tensor k_cache,
                         at::Tensor v_cache, at::Tensor block_tables,
                         at::Tensor token_seq, at::Tensor token_pos,
@@ -306,14 +327,18 @@ void paged_attn_prefill(at::Tensor out, at::Tensor q, at::Tensor k_cache,
   CHECK_GPU_DTYPE(block_tables, at::kInt);
   CHECK_GPU_DTYPE(token_seq, at::kInt);
   CHECK_GPU_DTYPE(token_pos, at::kInt);
+  check_prefill_args(out, q, k_cache, v_cache, block_tables, window);
   const int T = (int)q.size(0);
   const int QH = (int)q.size(1);
   const int HD = (int)q.size(2);
   const int KH = (int)k_cache.size(1);
   const int BS = (int)k_cache.size(2);
+  TORCH_CHECK(token_seq.numel() == T && token_pos.numel() == T,
+              "token_seq/token_pos must hold one entry per q row");
   TORCH_CHECK(QH % KH == 0, "GQA group mismatch");
   const int GQ = QH / KH;
   const int max_blocks = (int)block_tables.size(1);
+  if (T == 0) return;
   int rc = ps_paged_attn_prefill(
       out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
       block_tables.data_ptr(), token_seq.data_ptr(), token_pos.data_ptr(), T,
@@ -332,6 +357,11 @@ void paged_attn_prefill_mfma(at::Tensor out, at::Tensor q,
   cache_fp8(v_cache);
   CHECK_GPU_DTYPE(block_tables, at::kInt);
   CHECK_GPU_DTYPE(tile_info, at::kInt);
+  check_prefill_args(out, q, k_cache, v_cache, block_tables, window);
+  TORCH_CHECK(tile_info.dim() == 2 && tile_info.size(1) == 4,
+              "tile_info must be [num_tiles, 4]");
+  TORCH_CHECK(variant >= 3 && variant <= 5,
+              "mfma prefill variant must be 3, 4 or 5, got ", variant);
   const int QH = (int)q.size(1);
   const int HD = (int)q.size(2);
   const int KH = (int)k_cache.size(1);
@@ -339,6 +369,7 @@ void paged_attn_prefill_mfma(at::Tensor out, at::Tensor q,
   TORCH_CHECK(k_cache.size(2) == 16, "mfma prefill needs block_size 16");
   const int GQ = QH / KH;
   const int NT = (int)tile_info.size(0);
+  if (NT == 0) return;
   int rc;
   if (variant == 5) {
     // v5 with split-KV: allocate fp32 partial workspace when the launch
@@ -931,6 +962,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "8-phase deep-pipelined bf16 GEMM (out = x @ w.T)");
   m.def("skinny_gemm", &skinny_gemm,
         "Split-K MFMA GEMM for decode-shaped (M<=128) projections");
+  m.def("prefill_mfma32_splits", &ps_prefill_mfma32_splits,
+        "KV split count paged_attn_prefill_mfma variant 5 runs for (num_tiles, "
+        "KH, GQ)",
+        pybind11::arg("num_tiles"), pybind11::arg("KH"), pybind11::arg("GQ"));
   m.def("gemm8p_splits", &ps_gemm8p_splits,
         "Split-K depth gemm8p picks for (M, N, K); -1 if unsupported");
   m.def("skinny_gemm_splits", &ps_skinny_gemm_splits,

@@ -251,7 +251,13 @@ def paged_attn_prefill_mfma(
 ) -> torch.Tensor:
     """MFMA-tiled chunked prefill (GPU, head_dim 128 only). tile_info rows
     must be built with n_rows <= prefill_tile_rows() for the active
-    variant. `out` (contiguous, q's shape and dtype) receives the result."""
+    variant. `out` (contiguous, q's shape and dtype) receives the result.
+
+    Precondition: every row of q belongs to exactly one tile. Variant 5's
+    split-KV merge writes all q.shape[0] rows of `out` from per-row
+    partials that only a tile's workgroups fill in, so a row that no tile
+    covers would be merged from uninitialised workspace. q may be a row
+    slice of a wider buffer (stride(0) is free; heads must be packed)."""
     _require_ext()
     if out is None:
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
