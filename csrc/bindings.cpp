@@ -459,26 +459,49 @@ void reshape_and_cache(at::Tensor k, at::Tensor v, at::Tensor k_cache,
                        BS, kv_fp8, current_stream());
 }
 
-void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w) {
+// The fp32 split-K workspace ws[splits, M, N] of a GEMM, on `like`'s device:
+// allocated into `ws` and returned as a pointer, null when splits <= 1.
+void* splitk_workspace(at::Tensor& ws, const at::Tensor& like, int splits,
+                       int M, int N) {
+  if (splits <= 1) return nullptr;
+  ws = at::empty({(long)splits * M * N}, like.options().dtype(at::kFloat));
+  return ws.data_ptr();
+}
+
+// out[M, N] = x[M, K] @ w[N, K]^T in bf16 on one device; x may be a
+// row-strided view. skinny_gemm and gemm8p both read x and w as 16-byte
+// vectors at multiples of 8 elements from a row start. Sets M, N, K.
+void check_bf16_gemm(const at::Tensor& out, const at::Tensor& x,
+                     const at::Tensor& w, int& M, int& N, int& K) {
   CHECK_GPU_BF16(out);
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
               "x must be bf16");
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be 2D row-major");
   CHECK_GPU_BF16(w);
-  const int M = (int)x.size(0);
-  const int K = (int)x.size(1);
-  const int N = (int)w.size(0);
+  TORCH_CHECK(w.dim() == 2, "w must be [N, K]");
+  M = (int)x.size(0);
+  K = (int)x.size(1);
+  N = (int)w.size(0);
   TORCH_CHECK(w.size(1) == K, "K mismatch");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "out must be [", M, ", ", N, "]");
+  TORCH_CHECK(x.device() == w.device() && out.device() == x.device(),
+              "out, x and w must be on one device");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)w.data_ptr() % 16 == 0,
+              "x and w rows must be 16-byte aligned");
+  TORCH_CHECK(M <= 1 || x.stride(0) % 8 == 0,
+              "x row stride must be a multiple of 8 elements");
+}
+
+void skinny_gemm(at::Tensor out, at::Tensor x, at::Tensor w) {
+  int M, N, K;
+  check_bf16_gemm(out, x, w, M, N, K);
   const int splits = ps_skinny_gemm_splits(M, N, K);
   TORCH_CHECK(splits > 0, "unsupported skinny gemm shape M=", M, " N=", N,
               " K=", K);
-  void* ws_p = nullptr;
   at::Tensor ws;
-  if (splits > 1) {
-    ws = at::empty({(long)splits * M * N},
-                   x.options().dtype(at::kFloat));
-    ws_p = ws.data_ptr();
-  }
+  void* ws_p = splitk_workspace(ws, x, splits, M, N);
   int rc = ps_skinny_gemm(out.data_ptr(), ws_p, x.data_ptr(), w.data_ptr(),
                           M, N, K, x.stride(0), current_stream());
   TORCH_CHECK(rc == 0, "skinny gemm launch failed");
@@ -564,12 +587,8 @@ void skinny_gemm_fp8(at::Tensor out, at::Tensor xq, at::Tensor sx,
   TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 &&
                   (uintptr_t)wq.data_ptr() % 16 == 0,
               "xq and wq rows must be 16-byte aligned");
-  void* ws_p = nullptr;
   at::Tensor ws;
-  if (splits > 1) {
-    ws = at::empty({(long)splits * M * N}, sx.options());
-    ws_p = ws.data_ptr();
-  }
+  void* ws_p = splitk_workspace(ws, xq, splits, M, N);
   int rc = ps_skinny_gemm_fp8(out.data_ptr(), ws_p, xq.data_ptr(),
                               sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), M,
                               N, K, current_stream());
@@ -622,12 +641,8 @@ void skinny_gemm_w4(at::Tensor out, at::Tensor x, at::Tensor packed,
               " K=", K);
   TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0,
               "x rows must be 16-byte aligned");
-  void* ws_p = nullptr;
   at::Tensor ws;
-  if (splits > 1) {
-    ws = at::empty({(long)splits * M * N}, x.options().dtype(at::kFloat));
-    ws_p = ws.data_ptr();
-  }
+  void* ws_p = splitk_workspace(ws, x, splits, M, N);
   int rc = ps_skinny_gemm_w4(out.data_ptr(), ws_p, x.data_ptr(),
                              packed.data_ptr(), s.data_ptr(), z.data_ptr(),
                              M, N, K, current_stream());
@@ -653,24 +668,13 @@ void int4_dequant(at::Tensor out, at::Tensor packed, at::Tensor s,
 }
 
 void gemm8p(at::Tensor out, at::Tensor x, at::Tensor w) {
-  CHECK_GPU_BF16(out);
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
-              "x must be bf16");
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "x must be 2D row-major");
-  CHECK_GPU_BF16(w);
-  const int M = (int)x.size(0);
-  const int K = (int)x.size(1);
-  const int N = (int)w.size(0);
-  TORCH_CHECK(w.size(1) == K, "K mismatch");
+  int M, N, K;
+  check_bf16_gemm(out, x, w, M, N, K);
   const int splits = ps_gemm8p_splits(M, N, K);
   TORCH_CHECK(splits > 0, "unsupported gemm8p shape M=", M, " N=", N,
               " K=", K);
-  void* ws_p = nullptr;
   at::Tensor ws;
-  if (splits > 1) {
-    ws = at::empty({(long)splits * M * N}, x.options().dtype(at::kFloat));
-    ws_p = ws.data_ptr();
-  }
+  void* ws_p = splitk_workspace(ws, x, splits, M, N);
   int rc = ps_gemm8p(out.data_ptr(), ws_p, x.data_ptr(), w.data_ptr(), M, N,
                      K, x.stride(0), current_stream());
   TORCH_CHECK(rc == 0, "gemm8p launch failed");

@@ -30,24 +30,15 @@
 // on read"); the involution makes source and read permutations identical.
 //
 // Split-K for skinny-M shapes (decode batches): gridDim.y K-ranges write
-// fp32 partials to ws[S,M,N]; gemm8p_combine sums them to bf16. K must be a
+// fp32 partials to ws[S,M,N]; the combine kernel sums them to bf16. K must be a
 // multiple of 128 per split range (all Llama projections qualify).
 //
 // mfma_f32_16x16x32_bf16; A/B k-pattern lane=(l>>4)*8+i verified in
 // csrc/tools/mfma_probe.hip; C/D layout col=lane&15, row=(l>>4)*4+reg.
-#include "ps_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ps_g8bf16x8;
-typedef __attribute__((ext_vector_type(4))) float ps_g8f32x4;
-
-PS_DEV ps_g8bf16x8 ps_as_g8bf16(ps_bf16x8 u) {
-  union {
-    ps_bf16x8 u16;
-    ps_g8bf16x8 bf;
-  } v;
-  v.u16 = u;
-  return v.bf;
-}
+//
+// The operand type and the combine kernel are csrc/skinny_common.h's; the
+// split depth is csrc/splitk.h's.
+#include "skinny_common.h"
 
 // byte-offset swizzle within a 16 KiB half-tile (involution, 16B-granular).
 // Two candidates, A/B-selectable at compile time: the attention-style
@@ -79,8 +70,8 @@ PS_DEV unsigned ps_g8_lds_off(const void* p) {
 // pipeline each phase and reducing the schedule to 1-phase performance
 // (guide T3/T4 and common-mistake notes). Correct ordering is owned by the
 // phase barriers + the two counted vmcnt(4) waits.
-PS_DEV ps_g8bf16x8 ps_g8_ds_read_b128(unsigned addr) {
-  ps_g8bf16x8 r;
+PS_DEV ps_mfma_bf16x8 ps_g8_ds_read_b128(unsigned addr) {
+  ps_mfma_bf16x8 r;
   asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
   return r;
 }
@@ -166,7 +157,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(
   };
 
   // ---- accumulators: wave's 128x64 C block = 8 m-frags x 4 n-frags ----
-  ps_g8f32x4 acc[8][4];
+  ps_f32x4 acc[8][4];
 #pragma unroll
   for (int i = 0; i < 8; i++)
 #pragma unroll
@@ -193,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(
     const int brow0 = (wn & 1) * 64 + nh * 32;
     const unsigned a_base = a_lds0 + (buf * 2 + wm) * 16384;
     const unsigned b_base = b_lds0 + (buf * 2 + bh) * 16384;
-    ps_g8bf16x8 af[2][4], bf[2][2];
+    ps_mfma_bf16x8 af[2][4], bf[2][2];
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) {
 #pragma unroll
@@ -298,16 +289,6 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(
   }
 }
 
-__global__ void gemm8p_combine_kernel(unsigned short* __restrict__ out,
-                                      const float* __restrict__ ws, long MN,
-                                      int splits) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < splits; s++) acc += ws[(long)s * MN + i];
-  out[i] = ps_f32_to_bf16(acc);
-}
-
 extern "C" {
 
 // Returns split count the heuristic picks, or -1 if the shape is
@@ -316,18 +297,7 @@ extern "C" {
 int ps_gemm8p_splits(int M, int N, int K) {
   if (N % 256 != 0 || K % 128 != 0) return -1;
   const int mt = (M + 255) / 256;
-  const int nwg = mt * (N / 256);
-  int splits = 384 / nwg;
-  if (splits < 1) splits = 1;
-  const int kpairs = K / 128;
-  if (splits > kpairs) splits = kpairs;
-  // The kernel gives each split ceil(kpairs/splits) K-pairs, so trailing
-  // splits can come out empty; they return without writing their ws slice,
-  // which the combine kernel would still sum. Keep only the non-empty ones
-  // (a fixed point of the kernel's own per_split computation).
-  const int per_split = (kpairs + splits - 1) / splits;
-  splits = (kpairs + per_split - 1) / per_split;
-  return splits;
+  return ps_splitk_depth(K / 128, mt * (N / 256), 384, 1);
 }
 
 int ps_gemm8p(void* out_bf16, void* ws, const void* x, const void* w, int M,
@@ -340,11 +310,8 @@ int ps_gemm8p(void* out_bf16, void* ws, const void* x, const void* w, int M,
   gemm8p_kernel<<<grid, 512, 0, stream>>>(
       (unsigned short*)out_bf16, splits > 1 ? (float*)ws : nullptr,
       (const unsigned short*)x, (const unsigned short*)w, M, N, K, x_stride);
-  if (splits > 1) {
-    const long MN = (long)M * N;
-    gemm8p_combine_kernel<<<dim3((MN + 255) / 256), 256, 0, stream>>>(
-        (unsigned short*)out_bf16, (const float*)ws, MN, splits);
-  }
+  if (splits > 1)
+    ps_launch_splitk_combine(out_bf16, ws, M, N, splits, stream);
   return 0;
 }
 

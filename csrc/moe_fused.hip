@@ -23,22 +23,10 @@
 //   moe_combine     out[t] = sum_k w[t,k] * y[t*top_k+k], fixed k order.
 // mfma_f32_16x16x32_bf16; operand k-pattern as verified in
 // csrc/tools/mfma_probe.hip.
-#include "ps_common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ps_mbf16x8;
-typedef __attribute__((ext_vector_type(4))) float ps_mf32x4;
+#include "skinny_common.h"
 
 #define PS_MOE_MAX_PAIRS 1024
 #define PS_MOE_MAX_EXPERTS 64
-
-PS_DEV ps_mbf16x8 ps_as_mbf16(ps_bf16x8 u) {
-  union {
-    ps_bf16x8 u16;
-    ps_mbf16x8 bf;
-  } v;
-  v.u16 = u;
-  return v.bf;
-}
 
 // One workgroup of 1024 threads, thread p owns pair p = t*top_k + k.
 // Per wave, a ballot per expert gives the wave's count and each lane's rank
@@ -109,13 +97,8 @@ __global__ __launch_bounds__(256, 4) void moe_grouped_kernel(
   const int count = offsets[e + 1] - row0;  // workgroup-uniform
   if (count <= 0) return;
 
-  const int n0 = blockIdx.x * 64;
   const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int g = lane >> 4;
-  const int rc = lane & 15;
-  const int nrow = n0 + wave * 16 + rc;  // this lane's W row (B col)
+  const auto [wave, g, rc, nrow] = ps_skinny_lane_of();
   const int kchunks = K / 64;
   const long w_rows = (long)NB * N;
   const unsigned short* wg = w + ((long)e * w_rows + nrow) * K;
@@ -134,7 +117,7 @@ __global__ __launch_bounds__(256, 4) void moe_grouped_kernel(
     }
     __syncthreads();
 
-    ps_mf32x4 acc[NB][M_TILES];
+    ps_f32x4 acc[NB][M_TILES];
 #pragma unroll
     for (int b = 0; b < NB; b++)
 #pragma unroll
@@ -198,16 +181,16 @@ __global__ __launch_bounds__(256, 4) void moe_grouped_kernel(
 #pragma unroll
       for (int mt = 0; mt < M_TILES; mt++) {
         const int row = mt * 16 + rc;
-        ps_mbf16x8 a0 = ps_as_mbf16(
+        ps_mfma_bf16x8 a0 = ps_as_mfma_bf16(
             *(const ps_bf16x8*)(&a_lds[buf][row][(g ^ (row & 7)) * 8]));
-        ps_mbf16x8 a1 = ps_as_mbf16(
+        ps_mfma_bf16x8 a1 = ps_as_mfma_bf16(
             *(const ps_bf16x8*)(&a_lds[buf][row][((4 + g) ^ (row & 7)) * 8]));
 #pragma unroll
         for (int b = 0; b < NB; b++) {
           acc[b][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a0, ps_as_mbf16(bcur[b][0]), acc[b][mt], 0, 0, 0);
+              a0, ps_as_mfma_bf16(bcur[b][0]), acc[b][mt], 0, 0, 0);
           acc[b][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a1, ps_as_mbf16(bcur[b][1]), acc[b][mt], 0, 0, 0);
+              a1, ps_as_mfma_bf16(bcur[b][1]), acc[b][mt], 0, 0, 0);
         }
       }
       __builtin_amdgcn_s_setprio(0);

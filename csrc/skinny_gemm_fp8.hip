@@ -37,9 +37,11 @@
 // ds_write_b128 goes in groups of 8 consecutive lanes = 2 rows x 4 slots =
 // one 128-B span, conflict-free under its 32-bank rule with or without the
 // XOR.
-#include "ps_common.h"
+//
+// The K-range, lane coordinates, epilogue, combine loop and launch ladder are
+// csrc/skinny_common.h's; the split depth is csrc/splitk.h's.
+#include "skinny_common.h"
 
-typedef __attribute__((ext_vector_type(4))) float ps_f8acc;
 typedef __attribute__((ext_vector_type(2))) long ps_f8x16;  // 16 fp8, 16 B
 
 #define PS_F8_CPI 4  // 64-wide k-chunks per loop iteration
@@ -56,24 +58,16 @@ __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(
     const float* __restrict__ sw,           // [N]
     int M, int N, int K) {
   constexpr int MP = M_TILES * 16;  // padded M
-  const int n0 = blockIdx.x * 64;
-  const int splits = gridDim.y;
-  const int kchunks = K / 64;
-  const int per_split = (kchunks + splits - 1) / splits;
-  const int kc_begin = blockIdx.y * per_split;
-  const int kc_end = min(kchunks, kc_begin + per_split);
+  const auto [kc_begin, kc_end] =
+      ps_split_range_of(K / 64, gridDim.y, blockIdx.y);
   if (kc_begin >= kc_end) return;
 
   const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int g = lane >> 4;
-  const int rc = lane & 15;
-  const int nrow = n0 + wave * 16 + rc;  // this lane's W row (B col)
+  const auto [wave, g, rc, nrow] = ps_skinny_lane_of();
 
   __shared__ __align__(16) unsigned char x_lds[PS_F8_CPI][MP][64];
 
-  ps_f8acc acc[M_TILES];
+  ps_f32x4 acc[M_TILES];
 #pragma unroll
   for (int mt = 0; mt < M_TILES; mt++) acc[mt] = {0.f, 0.f, 0.f, 0.f};
 
@@ -120,62 +114,36 @@ __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(
     __syncthreads();
   }
 
-  // ---- epilogue (C layout: row = g*4 + r, col = rc of each 16x16 tile) ----
+  // sx[m] * sw[n] is formed first, in fp32, and applied once to the full sum
   const float swn = sw[nrow];
-#pragma unroll
-  for (int mt = 0; mt < M_TILES; mt++) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = mt * 16 + g * 4 + r;
-      if (m >= M) continue;
-      if (gridDim.y == 1) {
-        out_bf16[(long)m * N + nrow] =
-            ps_f32_to_bf16(acc[mt][r] * (sx[m] * swn));
-      } else {
-        ws[((long)blockIdx.y * M + m) * N + nrow] = acc[mt][r];
-      }
-    }
-  }
+  PS_SKINNY_EPILOGUE(v * (sx[m] * swn));
 }
+
+struct ps_f8_scale {
+  const float* sx;  // [M]
+  const float* sw;  // [N]
+  int N;
+  PS_DEV float operator()(float acc, long i) const {
+    return acc * (sx[i / N] * sw[i % N]);
+  }
+};
 
 __global__ __launch_bounds__(256) void skinny_fp8_combine_kernel(
     unsigned short* __restrict__ out,  // [M, N] bf16
     const float* __restrict__ ws,      // [S, M, N] fp32, unscaled
     const float* __restrict__ sx, const float* __restrict__ sw, long MN,
     int N, int splits) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < splits; s++) acc += ws[(long)s * MN + i];
-  out[i] = ps_f32_to_bf16(acc * (sx[i / N] * sw[i % N]));
+  ps_splitk_combine(out, ws, MN, splits, ps_f8_scale{sx, sw, N});
 }
 
 extern "C" {
 
 // Split depth for a shape, a function of (N, K) only; -1 if unsupported.
-// A split's chunk count is rounded up to whole PS_F8_CPI iterations, then
-// the count is taken to the fixed point of the kernel's own
-// per_split = ceil(kchunks / splits), so that no trailing split is empty:
-// an empty split writes no ws slice, and the combine kernel sums them all.
+// A split's chunk count is rounded up to whole PS_F8_CPI iterations.
 int ps_skinny_gemm_fp8_splits(int M, int N, int K) {
   if (M < 1 || M > 256 || N < 64 || K < 64 || N % 64 != 0 || K % 64 != 0)
     return -1;
-  const int kchunks = K / 64;
-  const int target_wgs = 1024;
-  int splits = target_wgs / (N / 64);
-  if (splits < 1) splits = 1;
-  if (splits > kchunks) splits = kchunks;
-  int per_split = (kchunks + splits - 1) / splits;
-  if (splits > 1)
-    per_split = (per_split + PS_F8_CPI - 1) / PS_F8_CPI * PS_F8_CPI;
-  splits = (kchunks + per_split - 1) / per_split;
-  for (;;) {
-    per_split = (kchunks + splits - 1) / splits;
-    const int s = (kchunks + per_split - 1) / per_split;
-    if (s == splits) break;
-    splits = s;
-  }
-  return splits;
+  return ps_splitk_depth(K / 64, N / 64, 1024, PS_F8_CPI);
 }
 
 // ws == nullptr forces splits = 1.
@@ -191,11 +159,7 @@ int ps_skinny_gemm_fp8(void* out_bf16, void* ws, const void* xq,
   skinny_gemm_fp8_kernel<MT><<<grid, block, 0, stream>>>(                  \
       (unsigned short*)out_bf16, (float*)ws, (const unsigned char*)xq,     \
       (const float*)sx, (const unsigned char*)wq, (const float*)sw, M, N, K)
-  if (M <= 16) PS_SGF(1);
-  else if (M <= 32) PS_SGF(2);
-  else if (M <= 64) PS_SGF(4);
-  else if (M <= 128) PS_SGF(8);
-  else PS_SGF(16);
+  PS_SKINNY_M_LADDER(M, PS_SGF);
 #undef PS_SGF
   if (splits > 1) {
     const long MN = (long)M * N;

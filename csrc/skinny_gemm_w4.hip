@@ -42,21 +42,28 @@
 // groups that hold 8 rows at slot 4j+g and 8 other rows at slot 4j+(g^1);
 // the XOR sends those 16 (row, slot) pairs to 16 different slots of the
 // 256-B bank row.
-#include "ps_common.h"
+//
+// The K-range, lane coordinates, epilogue, combine kernel and launch ladder
+// are csrc/skinny_common.h's; the split depth is csrc/splitk.h's.
+#include "skinny_common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 ps_w4bf16x8;
-typedef __attribute__((ext_vector_type(4))) float ps_w4acc;
 typedef __attribute__((ext_vector_type(4))) unsigned int ps_w4u32x4;  // 16 B
 
 #define PS_W4_GROUP 128
 #define PS_W4_MAX_CPI 4  // most 128-wide groups per loop iteration
 
+// groups per iteration of the M_TILES instantiation:
+// (M_TILES, CPI) = (1, 4), (2, 2), (4, 2), (8, 1), (16, 1)
+constexpr int ps_w4_cpi(int m_tiles) {
+  return m_tiles == 1 ? 4 : m_tiles > 4 ? 1 : 2;
+}
+
 // eight nibbles of w -> (q - z) * s as eight bf16, element i from nibble i
-PS_DEV ps_w4bf16x8 ps_w4_dequant8(unsigned int w, float s, float nzs) {
+PS_DEV ps_mfma_bf16x8 ps_w4_dequant8(unsigned int w, float s, float nzs) {
   const unsigned int lo = w & 0x0f0f0f0fu;         // elements 0, 2, 4, 6
   const unsigned int hi = (w >> 4) & 0x0f0f0f0fu;  // elements 1, 3, 5, 7
   union {
-    ps_w4bf16x8 bf;
+    ps_mfma_bf16x8 bf;
     unsigned int u[4];
   } o;
 #pragma unroll
@@ -80,24 +87,17 @@ __global__ __launch_bounds__(256) void skinny_gemm_w4_kernel(
     const unsigned char* __restrict__ zp,     // [N, K/128]
     int M, int N, int K) {
   constexpr int MP = M_TILES * 16;  // padded M
-  const int n0 = blockIdx.x * 64;
-  const int splits = gridDim.y;
   const int kgroups = K / PS_W4_GROUP;
-  const int per_split = (kgroups + splits - 1) / splits;
-  const int kc_begin = blockIdx.y * per_split;
-  const int kc_end = min(kgroups, kc_begin + per_split);
+  const auto [kc_begin, kc_end] =
+      ps_split_range_of(kgroups, gridDim.y, blockIdx.y);
   if (kc_begin >= kc_end) return;
 
   const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int lane = tid & 63;
-  const int g = lane >> 4;
-  const int rc = lane & 15;
-  const int nrow = n0 + wave * 16 + rc;  // this lane's W row (B col)
+  const auto [wave, g, rc, nrow] = ps_skinny_lane_of();
 
   __shared__ __align__(16) unsigned short x_lds[CPI][MP][PS_W4_GROUP];
 
-  ps_w4acc acc[M_TILES];
+  ps_f32x4 acc[M_TILES];
 #pragma unroll
   for (int mt = 0; mt < M_TILES; mt++) acc[mt] = {0.f, 0.f, 0.f, 0.f};
 
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_w4_kernel(
     for (int c = 0; c < CPI; c++) {
       if (c < nc) {
         // ---- B-frags built in registers ----
-        ps_w4bf16x8 bf[4];
+        ps_mfma_bf16x8 bf[4];
 #pragma unroll
         for (int j = 0; j < 4; j++)
           bf[j] = ps_w4_dequant8(b[c][j], s[c], nzs[c]);
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_w4_kernel(
           const int row = mt * 16 + rc;
 #pragma unroll
           for (int j = 0; j < 4; j++) {
-            const ps_w4bf16x8 a = *(const ps_w4bf16x8*)(
+            const ps_mfma_bf16x8 a = *(const ps_mfma_bf16x8*)(
                 &x_lds[c][row][((4 * j + g) ^ (row & 15)) * 8]);
             acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 a, bf[j], acc[mt], 0, 0, 0);
@@ -159,31 +159,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_w4_kernel(
     __syncthreads();
   }
 
-  // ---- epilogue (C layout: row = g*4 + r, col = rc of each 16x16 tile) ----
-#pragma unroll
-  for (int mt = 0; mt < M_TILES; mt++) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = mt * 16 + g * 4 + r;
-      if (m >= M) continue;
-      if (gridDim.y == 1) {
-        out_bf16[(long)m * N + nrow] = ps_f32_to_bf16(acc[mt][r]);
-      } else {
-        ws[((long)blockIdx.y * M + m) * N + nrow] = acc[mt][r];
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void skinny_w4_combine_kernel(
-    unsigned short* __restrict__ out,  // [M, N] bf16
-    const float* __restrict__ ws,      // [S, M, N] fp32
-    long MN, int splits) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= MN) return;
-  float acc = 0.f;
-  for (int s = 0; s < splits; s++) acc += ws[(long)s * MN + i];
-  out[i] = ps_f32_to_bf16(acc);
+  PS_SKINNY_EPILOGUE(v);
 }
 
 // packed + s + z -> W_deq[N, K] bf16. One thread per 16-B packed load (32
@@ -208,37 +184,18 @@ __global__ __launch_bounds__(256) void int4_dequant_kernel(
   unsigned short* o = out + n * K + (long)c * PS_W4_GROUP + g * 8;
 #pragma unroll
   for (int j = 0; j < 4; j++)
-    *(ps_w4bf16x8*)(o + 32 * j) = ps_w4_dequant8(w[j], s, nzs);
+    *(ps_mfma_bf16x8*)(o + 32 * j) = ps_w4_dequant8(w[j], s, nzs);
 }
 
 extern "C" {
 
 // Split depth for a shape, a function of (N, K) only; -1 if unsupported.
-// A split's group count is rounded up to whole PS_W4_MAX_CPI iterations,
-// then the count is taken to the fixed point of the kernel's own
-// per_split = ceil(kgroups / splits), so that no trailing split is empty:
-// an empty split writes no ws slice, and the combine kernel sums them all.
+// A split's group count is rounded up to whole PS_W4_MAX_CPI iterations.
 int ps_skinny_gemm_w4_splits(int M, int N, int K) {
   if (M < 1 || M > 256 || N < 64 || K < PS_W4_GROUP || N % 64 != 0 ||
       K % PS_W4_GROUP != 0)
     return -1;
-  const int kgroups = K / PS_W4_GROUP;
-  const int target_wgs = 1024;
-  int splits = target_wgs / (N / 64);
-  if (splits < 1) splits = 1;
-  if (splits > kgroups) splits = kgroups;
-  int per_split = (kgroups + splits - 1) / splits;
-  if (splits > 1)
-    per_split =
-        (per_split + PS_W4_MAX_CPI - 1) / PS_W4_MAX_CPI * PS_W4_MAX_CPI;
-  splits = (kgroups + per_split - 1) / per_split;
-  for (;;) {
-    per_split = (kgroups + splits - 1) / splits;
-    const int s = (kgroups + per_split - 1) / per_split;
-    if (s == splits) break;
-    splits = s;
-  }
-  return splits;
+  return ps_splitk_depth(K / PS_W4_GROUP, N / 64, 1024, PS_W4_MAX_CPI);
 }
 
 // ws == nullptr forces splits = 1.
@@ -251,22 +208,15 @@ int ps_skinny_gemm_w4(void* out_bf16, void* ws, const void* x,
   if (ws == nullptr) splits = 1;
   dim3 grid(N / 64, splits);
   dim3 block(256);
-#define PS_SGW(MT, CPI)                                                     \
-  skinny_gemm_w4_kernel<MT, CPI><<<grid, block, 0, stream>>>(               \
+#define PS_SGW(MT)                                                          \
+  skinny_gemm_w4_kernel<MT, ps_w4_cpi(MT)><<<grid, block, 0, stream>>>(     \
       (unsigned short*)out_bf16, (float*)ws, (const unsigned short*)x,      \
       (const unsigned char*)packed, (const unsigned short*)scales,          \
       (const unsigned char*)zeros, M, N, K)
-  if (M <= 16) PS_SGW(1, 4);
-  else if (M <= 32) PS_SGW(2, 2);
-  else if (M <= 64) PS_SGW(4, 2);
-  else if (M <= 128) PS_SGW(8, 1);
-  else PS_SGW(16, 1);
+  PS_SKINNY_M_LADDER(M, PS_SGW);
 #undef PS_SGW
-  if (splits > 1) {
-    const long MN = (long)M * N;
-    skinny_w4_combine_kernel<<<dim3((MN + 255) / 256), 256, 0, stream>>>(
-        (unsigned short*)out_bf16, (const float*)ws, MN, splits);
-  }
+  if (splits > 1)
+    ps_launch_splitk_combine(out_bf16, ws, M, N, splits, stream);
   return 0;
 }
 

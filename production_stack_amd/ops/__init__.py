@@ -366,8 +366,9 @@ def kv_dequant(
 
 
 def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """out = x @ w.T for decode-shaped M<=128 (weight-stream-bound GEMMs
-    where hipBLASLt tiles poorly — see csrc/skinny_gemm.hip). GPU only."""
+    """out = x @ w.T for decode-shaped 1 <= M <= 256, N and K multiples of
+    64 (weight-stream-bound GEMMs where hipBLASLt tiles poorly — see
+    csrc/skinny_gemm.hip). GPU only."""
     _require_ext()
     out = torch.empty(
         (x.shape[0], w.shape[0]), dtype=torch.bfloat16, device=x.device

@@ -25,7 +25,8 @@ _POLICY: Dict[Tuple[int, int, int], int] = {}
 
 
 def _eligible(M: int, N: int, K: int) -> bool:
-    return M <= 256 and N % 64 == 0 and K % 64 == 0
+    return (1 <= M <= 256 and N >= 64 and K >= 64
+            and N % 64 == 0 and K % 64 == 0)
 
 
 def _eligible_8p(M: int, N: int, K: int) -> bool:

@@ -282,6 +282,22 @@ def test_skinny_rejects(M, N, K):
         ops.skinny_gemm(_bf16(M, K), _bf16(N, K))
 
 
+@pytest.mark.parametrize("M,N,K", [(16, 0, 64), (16, 64, 0)])
+def test_skinny_rejects_empty_dims(M, N, K):
+    """Host only: N = 0 and K = 0 fail the accept rule before any launch."""
+    assert _splits("skinny", M, N, K) == -1
+    with pytest.raises(RuntimeError):
+        ops.skinny_gemm(_bf16(M, K), _bf16(N, K))
+
+
+@pytest.mark.parametrize("shape", [(16, 128), (32, 64), (16 * 64,)])
+def test_skinny_rejects_out_shape(shape):
+    """Host only: out must be [M, N], also where its element count fits."""
+    M, N, K = 16, 64, 64
+    with pytest.raises(RuntimeError):
+        _C().skinny_gemm(_bf16(*shape), _bf16(M, K), _bf16(N, K))
+
+
 def test_policy_eligibility_matches_kernels():
     """Host only: the autotuner offers a kernel exactly where it accepts."""
     dims = (32, 64, 96, 128, 192, 256, 320, 384, 512, 4096, 14336)
