@@ -105,6 +105,14 @@ int ps_fused_moe(void* out, void* offsets, void* sorted_pairs, void* act,
                  const void* w_down, const void* topk_ids, int ids_i64,
                  const void* topk_w, int T, int top_k, int E, int H, int I,
                  hipStream_t stream);
+int ps_fused_moe_w4_supported(int T, int top_k, int E, int H, int I);
+int ps_fused_moe_w4_splits(int top_k, int H, int I);
+int ps_fused_moe_w4(void* out, void* offsets, void* sorted_pairs, void* act,
+                    void* y, const void* x, const void* gu_packed,
+                    const void* gu_s, const void* gu_z, const void* dn_packed,
+                    const void* dn_s, const void* dn_z, const void* topk_ids,
+                    int ids_i64, const void* topk_w, int T, int top_k, int E,
+                    int H, int I, hipStream_t stream);
 int ps_resolve_placeholders(void* tokens, const void* prev_row,
                             const void* prev_tokens, long n, long n_prev,
                             hipStream_t stream);
@@ -778,6 +786,106 @@ void fused_moe(at::Tensor out, at::Tensor offsets, at::Tensor sorted_pairs,
   TORCH_CHECK(rc == 0, "fused_moe launch rejected");
 }
 
+bool fused_moe_int4_supported(int64_t T, int64_t top_k, int64_t E, int64_t H,
+                              int64_t I) {
+  const int64_t lim = 1 << 30;
+  if (T > lim || top_k > lim || E > lim || H > lim || I > lim) return false;
+  return ps_fused_moe_w4_supported((int)T, (int)top_k, (int)E, (int)H,
+                                   (int)I) != 0;
+}
+
+// split depth of the down GEMM, i.e. the leading extent of the y scratch
+int64_t fused_moe_int4_splits(int64_t top_k, int64_t H, int64_t I) {
+  const int64_t lim = 1 << 30;
+  if (top_k > lim || H > lim || I > lim) return -1;
+  return ps_fused_moe_w4_splits((int)top_k, (int)H, (int)I);
+}
+
+// packed [E, N, K/2] uint8, s [E, N, K/128] bf16, z [E, N, K/128] uint8 of a
+// stack of int4 expert weights
+void check_int4_experts(const char* what, const at::Tensor& packed,
+                        const at::Tensor& s, const at::Tensor& z, int64_t E,
+                        int64_t N, int64_t K) {
+  CHECK_GPU_DTYPE(packed, at::kByte);
+  CHECK_GPU_BF16(s);
+  CHECK_GPU_DTYPE(z, at::kByte);
+  TORCH_CHECK(packed.dim() == 3 && packed.size(0) == E &&
+                  packed.size(1) == N && packed.size(2) * 2 == K,
+              "fused_moe_int4: ", what, " packed must be [", E, ", ", N, ", ",
+              K / 2, "]");
+  TORCH_CHECK(s.dim() == 3 && s.size(0) == E && s.size(1) == N &&
+                  s.size(2) * 128 == K,
+              "fused_moe_int4: ", what, " s must be [", E, ", ", N, ", ",
+              K / 128, "]");
+  TORCH_CHECK(z.sizes() == s.sizes(), "fused_moe_int4: ", what,
+              " z must have the shape of s");
+  TORCH_CHECK(packed.device() == s.device() && packed.device() == z.device(),
+              "fused_moe_int4: ", what, " packed, s and z must be on one "
+              "device");
+  TORCH_CHECK((uintptr_t)packed.data_ptr() % 16 == 0, "fused_moe_int4: ",
+              what, " packed rows must be 16-byte aligned");
+}
+
+// scratch tensors come from the caller so they land in the graph pool
+// under capture
+void fused_moe_int4(at::Tensor out, at::Tensor offsets,
+                    at::Tensor sorted_pairs, at::Tensor act, at::Tensor y,
+                    at::Tensor x, at::Tensor gu_packed, at::Tensor gu_s,
+                    at::Tensor gu_z, at::Tensor dn_packed, at::Tensor dn_s,
+                    at::Tensor dn_z, at::Tensor topk_ids, at::Tensor topk_w) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_BF16(x);
+  CHECK_GPU_BF16(act);
+  CHECK_GPU_DTYPE(y, at::kFloat);
+  CHECK_GPU_DTYPE(offsets, at::kInt);
+  CHECK_GPU_DTYPE(sorted_pairs, at::kInt);
+  CHECK_GPU_DTYPE(topk_w, at::kFloat);
+  TORCH_CHECK(topk_ids.is_cuda() && topk_ids.is_contiguous() &&
+                  (topk_ids.scalar_type() == at::kLong ||
+                   topk_ids.scalar_type() == at::kInt),
+              "topk_ids must be contiguous int32/int64 on the GPU");
+  TORCH_CHECK(x.dim() == 2 && topk_ids.dim() == 2 && gu_packed.dim() == 3 &&
+                  dn_packed.dim() == 3,
+              "fused_moe_int4: x [T,H], topk_ids [T,k], gate_up packed "
+              "[E,2I,H/2], down packed [E,H,I/2]");
+  const int64_t T = x.size(0), H = x.size(1);
+  const int64_t top_k = topk_ids.size(1);
+  const int64_t E = gu_packed.size(0);
+  const int64_t I = dn_packed.size(2) * 2;
+  TORCH_CHECK(topk_ids.size(0) == T && topk_w.dim() == 2 &&
+                  topk_w.size(0) == T && topk_w.size(1) == top_k,
+              "fused_moe_int4: routing shape mismatch");
+  TORCH_CHECK(fused_moe_int4_supported(T, top_k, E, H, I),
+              "unsupported fused_moe_int4 shape T=", T, " top_k=", top_k,
+              " E=", E, " H=", H, " I=", I);
+  check_int4_experts("gate_up", gu_packed, gu_s, gu_z, E, 2 * I, H);
+  check_int4_experts("down", dn_packed, dn_s, dn_z, E, H, I);
+  TORCH_CHECK(x.device() == gu_packed.device() &&
+                  x.device() == dn_packed.device() &&
+                  x.device() == topk_ids.device() &&
+                  x.device() == topk_w.device() && x.device() == out.device(),
+              "fused_moe_int4: all tensors must be on one device");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 &&
+                  (uintptr_t)act.data_ptr() % 16 == 0 &&
+                  (uintptr_t)y.data_ptr() % 16 == 0,
+              "fused_moe_int4: x, act and y must be 16-byte aligned");
+  const int64_t P = T * top_k;
+  const int64_t S = fused_moe_int4_splits(top_k, H, I);
+  TORCH_CHECK(S >= 1, "fused_moe_int4: no split depth for this shape");
+  TORCH_CHECK(out.numel() == T * H && offsets.numel() >= E + 1 &&
+                  sorted_pairs.numel() >= P && act.numel() >= P * I &&
+                  y.numel() >= S * P * H,
+              "fused_moe_int4: output/scratch too small");
+  int rc = ps_fused_moe_w4(
+      out.data_ptr(), offsets.data_ptr(), sorted_pairs.data_ptr(),
+      act.data_ptr(), y.data_ptr(), x.data_ptr(), gu_packed.data_ptr(),
+      gu_s.data_ptr(), gu_z.data_ptr(), dn_packed.data_ptr(),
+      dn_s.data_ptr(), dn_z.data_ptr(), topk_ids.data_ptr(),
+      topk_ids.scalar_type() == at::kLong ? 1 : 0, topk_w.data_ptr(), (int)T,
+      (int)top_k, (int)E, (int)H, (int)I, current_stream());
+  TORCH_CHECK(rc == 0, "fused_moe_int4 launch rejected");
+}
+
 void kv_quant(at::Tensor out, at::Tensor scales, at::Tensor in) {
   CHECK_GPU_DTYPE(out, at::kChar);
   CHECK_GPU_DTYPE(scales, at::kFloat);
@@ -994,4 +1102,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Grouped MoE expert MLP (align + gate_up/SiLU + down + combine)");
   m.def("fused_moe_supported", &fused_moe_supported,
         "Whether fused_moe accepts (T, top_k, E, H, I)");
+  m.def("fused_moe_int4", &fused_moe_int4,
+        "Grouped MoE expert MLP on int4 weight-only (group 128) experts");
+  m.def("fused_moe_int4_supported", &fused_moe_int4_supported,
+        "Whether fused_moe_int4 accepts (T, top_k, E, H, I)");
+  m.def("fused_moe_int4_splits", &fused_moe_int4_splits,
+        "Split-K depth of fused_moe_int4's down GEMM for (top_k, H, I); -1 "
+        "if unsupported");
 }

@@ -30,3 +30,15 @@ static inline int ps_splitk_depth(int units, int wgs_per_split, int target_wgs,
     splits = s;
   }
 }
+
+// ps_splitk_depth with at most `max_splits` K-ranges, for a caller whose
+// workspace grows with the depth (moe_fused_w4.hip). Lowering the target
+// bounds the first guess, and the fixed point only ever lowers the count, so
+// the result keeps every property above.
+static inline int ps_splitk_depth_capped(int units, int wgs_per_split,
+                                         int target_wgs, int round_to,
+                                         int max_splits) {
+  const long cap = (long)wgs_per_split * max_splits;
+  if (cap < target_wgs) target_wgs = (int)cap;
+  return ps_splitk_depth(units, wgs_per_split, target_wgs, round_to);
+}

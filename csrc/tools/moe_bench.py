@@ -7,6 +7,11 @@ layer computes it either way. Windows alternate between the paths and the
 median window is reported. The fused path's effective weight bandwidth is
 (bytes of the experts that received a token) / (time of the fused op alone).
 
+--int4 adds csrc/moe_fused_w4.hip on the same layer quantized to int4
+(W4A16): the fused op alone, in windows alternating with the bf16 fused op,
+its bandwidth over the int4 bytes (packed nibbles, scales and zero points) of
+the experts that received a token, and the bf16/int4 time ratio.
+
 --engine adds mini-mixtral decode steps/s with moe_backend=loop,
 fused + enforce_eager and fused + hipGraphs (kernel effect vs capture).
 """
@@ -40,7 +45,7 @@ def _window(fn, iters):
     return (time.perf_counter() - t0) / iters
 
 
-def bench_layer(Ts, iters, windows):
+def bench_layer(Ts, iters, windows, int4=False):
     from production_stack_amd.engine.models.llama import LlamaLayer
 
     cfg = dataclasses.replace(ARCHITECTURES["mixtral-8x7b"], num_layers=1)
@@ -56,6 +61,13 @@ def bench_layer(Ts, iters, windows):
     print(f"layer: E={E} H={H} I={I} top_k={K}  "
           f"({expert_bytes / 1e6:.0f} MB per expert)")
     print("   T  experts   loop us  fused us  graph us  op us   op GB/s")
+    if int4:
+        with torch.no_grad():
+            gu4 = ops.int4_quantize_experts(layer.experts_gate_up.data)
+            dn4 = ops.int4_quantize_experts(layer.experts_down.data)
+        # one expert's slice of each of the six tensors
+        int4_bytes = sum(t[0].nbytes for t in gu4 + dn4)
+        int4_rows = []
     for T in Ts:
         x = torch.randn(T, H, device="cuda").to(torch.bfloat16)
 
@@ -87,18 +99,40 @@ def bench_layer(Ts, iters, windows):
         with torch.cuda.graph(graph):
             run("fused")
         graph.replay()
-        t = {"loop": [], "fused": [], "graph": [], "op": []}
+        t = {"loop": [], "fused": [], "graph": [], "op": [], "op4": []}
+        if int4:
+            def op4():
+                return ops.fused_moe_int4(x, gu4, dn4, sel, w)
+
+            for _ in range(10):
+                op4()
         for _ in range(windows):
+            if int4:
+                t["op4"].append(_window(op4, iters))
             t["loop"].append(_window(lambda: run("loop"), iters))
             t["fused"].append(_window(lambda: run("fused"), iters))
             t["graph"].append(_window(graph.replay, iters))
             t["op"].append(_window(op, iters))
-        m = {k: statistics.median(v) for k, v in t.items()}
+        m = {k: statistics.median(v) for k, v in t.items() if v}
         gbs = active * expert_bytes / m["op"] / 1e9
         print(f"{T:4d}  {active:7d}  {m['loop'] * 1e6:8.1f}  "
               f"{m['fused'] * 1e6:8.1f}  {m['graph'] * 1e6:8.1f}  "
               f"{m['op'] * 1e6:6.1f}  {gbs:8.0f}   "
               f"(max |fused-loop| {diff:.4f})")
+        if int4:
+            int4_rows.append(
+                f"{T:4d}  {active:7d}  {m['op'] * 1e6:10.1f}  "
+                f"{m['op4'] * 1e6:10.1f}  "
+                f"{active * int4_bytes / m['op4'] / 1e12:9.2f}  "
+                f"{m['op'] / m['op4']:9.2f}"
+            )
+    if int4:
+        from production_stack_amd import _C
+
+        print(f"int4 experts: {int4_bytes / 1e6:.0f} MB per expert, split-K "
+              f"depth of the down GEMM {_C.fused_moe_int4_splits(K, H, I)}")
+        print("   T  experts  bf16 op us  int4 op us  int4 TB/s  bf16/int4")
+        print("\n".join(int4_rows))
 
 
 def bench_engine(batch, steps):
@@ -146,6 +180,7 @@ if __name__ == "__main__":
     ap.add_argument("--T", type=int, nargs="+", default=[1, 8, 64, 256])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--int4", action="store_true")
     ap.add_argument("--engine", action="store_true")
     ap.add_argument("--engine-batch", type=int, default=8)
     ap.add_argument("--engine-steps", type=int, default=128)
@@ -153,6 +188,6 @@ if __name__ == "__main__":
     args = ap.parse_args()
     assert torch.cuda.is_available(), "moe_bench needs a GPU"
     if not args.skip_layer:
-        bench_layer(args.T, args.iters, args.windows)
+        bench_layer(args.T, args.iters, args.windows, args.int4)
     if args.engine:
         bench_engine(args.engine_batch, args.engine_steps)

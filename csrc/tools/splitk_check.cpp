@@ -4,7 +4,8 @@
 //   ./splitk_check
 // For units and wgs_per_split in 1..512, round_to in {1, 2, 4} and target_wgs
 // in {384, 1024} it checks what the GEMM kernels and their combine kernel
-// rely on. Exits non-zero if any case fails.
+// rely on, and the same for ps_splitk_depth_capped at 8 splits, the depth of
+// moe_fused_w4.hip's down GEMM. Exits non-zero if any case fails.
 #include <cstdio>
 #include <initializer_list>
 
@@ -27,8 +28,14 @@ int failures = 0;
 
 int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-void check(int units, int wgs, int target, int round) {
-  const int splits = ps_splitk_depth(units, wgs, target, round);
+void check(int units, int wgs, int target, int round, int max_splits = 0) {
+  int splits = ps_splitk_depth(units, wgs, target, round);
+  if (max_splits) {  // the capped depth is the plain one at a lower target
+    splits = ps_splitk_depth_capped(units, wgs, target, round, max_splits);
+    EXPECT(splits <= max_splits);
+    if (wgs * max_splits < target) target = wgs * max_splits;
+    EXPECT(splits == ps_splitk_depth(units, wgs, target, round));
+  }
   EXPECT(1 <= splits && splits <= units);
   if (splits < 1) return;
 
@@ -67,8 +74,10 @@ int main() {
   for (int target : {384, 1024})
     for (int round : {1, 2, 4})
       for (int units = 1; units <= 512; ++units)
-        for (int wgs = 1; wgs <= 512; ++wgs, ++cases)
+        for (int wgs = 1; wgs <= 512; ++wgs, ++cases) {
           check(units, wgs, target, round);
+          check(units, wgs, target, round, 8);
+        }
   if (failures) {
     std::printf("%d check(s) failed\n", failures);
     return 1;

@@ -385,7 +385,9 @@ class EngineConfig:
     # weight quantization: None (bf16), "fp8" (OCP e4m3 weights +
     # dynamic per-tensor activation quant through the fp8 MFMA pipe) or
     # "int4" (weight-only, group 128, bf16 scales + zero points; bf16
-    # activations, so LoRA works). Anything else raises at engine start.
+    # activations, so LoRA works; covers the dense projections and the
+    # experts of a MoE layer, the router stays bf16). Anything else raises
+    # at engine start.
     quantization: Optional[str] = None
     # fp8 GEMM backend, read only when quantization == "fp8": "scaled_mm"
     # (torch._scaled_mm / hipBLASLt) or "native" (csrc/skinny_gemm_fp8.hip
@@ -394,7 +396,8 @@ class EngineConfig:
     fp8_gemm: str = "scaled_mm"
     # sparse-MoE expert dispatch: "loop" (per-expert Python loop over
     # hipBLASLt GEMMs; host syncs, so no decode hipGraphs) or "fused"
-    # (csrc/moe_fused.hip grouped kernels for steps with T*top_k <= 1024;
+    # (csrc/moe_fused.hip grouped kernels, csrc/moe_fused_w4.hip on int4
+    # experts, for steps with T*top_k <= 1024;
     # routing stays on the device, decode hipGraphs are captured)
     moe_backend: str = "loop"
     # draft-model speculative decoding (engine/draft.py): architecture

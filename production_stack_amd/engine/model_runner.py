@@ -202,7 +202,15 @@ class ModelRunner:
                 ops.FUSED_MOE_MAX_PAIRS // self.model_cfg.num_experts_per_tok,
             )
             cfg = self.model_cfg
-            if not ops.fused_moe_supported(
+            layer0 = self.model.layers[0]
+            int4_experts = "experts_gate_up" in (
+                getattr(layer0, "int4_w", None) or {}
+            )
+            supported = (
+                ops.fused_moe_int4_supported if int4_experts
+                else ops.fused_moe_supported
+            )
+            if not supported(
                 max_batch, cfg.num_experts_per_tok, cfg.num_experts,
                 cfg.hidden_size, self.model.layers[0].inter,
             ):

@@ -416,19 +416,47 @@ class LlamaLayer(nn.Module):
         probs = torch.softmax(logits, dim=-1)
         weights, sel = torch.topk(probs, self.top_k, dim=-1)
         weights = weights / weights.sum(dim=-1, keepdim=True)
-        if (
-            self.moe_backend == "fused"
-            and x.is_cuda
-            and ops.fused_moe_supported(
-                x.shape[0], self.top_k, self.n_experts, x.shape[1],
-                self.inter,
-            )
-        ):
-            # one fixed launch sequence, routing consumed on the device
-            # (csrc/moe_fused.hip); larger steps keep the loop below
-            return ops.fused_moe(
-                x, self.experts_gate_up, self.experts_down, sel, weights
-            )
+        int4 = getattr(self, "int4_w", None) or {}
+        if "experts_gate_up" in int4:
+            # int4 weight-only experts (quantize_int4)
+            gu, dn = int4["experts_gate_up"], int4["experts_down"]
+            if (
+                self.moe_backend == "fused"
+                and x.is_cuda
+                and ops.fused_moe_int4_supported(
+                    x.shape[0], self.top_k, self.n_experts, x.shape[1],
+                    self.inter,
+                )
+            ):
+                # csrc/moe_fused_w4.hip; larger steps keep the loop below
+                return ops.fused_moe_int4(x, gu, dn, sel, weights)
+
+            def gate_up_of(xe, e):
+                return ops.int4_linear(xe, gu[0][e], gu[1][e], gu[2][e])
+
+            def down_of(act, e):
+                return ops.int4_linear(act, dn[0][e], dn[1][e], dn[2][e])
+        else:
+            if (
+                self.moe_backend == "fused"
+                and x.is_cuda
+                and ops.fused_moe_supported(
+                    x.shape[0], self.top_k, self.n_experts, x.shape[1],
+                    self.inter,
+                )
+            ):
+                # one fixed launch sequence, routing consumed on the device
+                # (csrc/moe_fused.hip); larger steps keep the loop below
+                return ops.fused_moe(
+                    x, self.experts_gate_up, self.experts_down, sel, weights
+                )
+
+            def gate_up_of(xe, e):
+                return gemm_policy.linear(xe, self.experts_gate_up[e])
+
+            def down_of(act, e):
+                return gemm_policy.linear(act, self.experts_down[e])
+
         weights = weights.to(x.dtype)
         out = torch.zeros_like(x)
         for e in range(self.n_experts):
@@ -437,10 +465,8 @@ class LlamaLayer(nn.Module):
             if rows.numel() == 0:
                 continue
             xe = x.index_select(0, rows)
-            act = ops.silu_and_mul(
-                gemm_policy.linear(xe, self.experts_gate_up[e])
-            )
-            ye = gemm_policy.linear(act, self.experts_down[e])
+            act = ops.silu_and_mul(gate_up_of(xe, e))
+            ye = down_of(act, e)
             w = (weights * mask.to(weights.dtype)).sum(-1)
             out.index_add_(
                 0, rows, ye * w.index_select(0, rows).unsqueeze(-1)
@@ -545,8 +571,11 @@ class LlamaForCausalLM(nn.Module):
         "W4A16" class). Activations stay bf16, so norms, RoPE, attention
         and both LoRA paths run unchanged. A projection whose local shape
         the int4 GEMM does not take (N % 64 or K % 128 non-zero, odd TP
-        shards) stays bf16. MoE experts, embedding, lm_head and norms stay
-        bf16, as for fp8."""
+        shards) stays bf16. The experts of a MoE layer are quantized as two
+        stacks, int4_w["experts_gate_up"] and int4_w["experts_down"]
+        (ops.int4_quantize_experts), both or neither: a local hidden or
+        intermediate width that is no multiple of 128 keeps both bf16. The
+        router (moe_gate), embedding, lm_head and norms stay bf16."""
         for layer in self.layers:
             int4_w = {}
             proj_names = [("qkv", "qkv_proj"), ("o", "o_proj")]
@@ -567,6 +596,20 @@ class LlamaForCausalLM(nn.Module):
                 # free the bf16 copy, as quantize_fp8 does
                 w.data = torch.empty(0, dtype=torch.bfloat16,
                                      device=w.device)
+            if layer.n_experts:
+                H, I = layer.experts_down.shape[1:]
+                if H % ops.INT4_GROUP or I % ops.INT4_GROUP:
+                    logger.warning(
+                        "layer %d experts (H=%d, I=%d) are not "
+                        "int4-quantizable (needs both %% %d == 0); kept bf16",
+                        layer.layer_idx, H, I, ops.INT4_GROUP,
+                    )
+                else:
+                    for key in ("experts_gate_up", "experts_down"):
+                        w = getattr(layer, key)
+                        int4_w[key] = ops.int4_quantize_experts(w.data)
+                        w.data = torch.empty(0, dtype=torch.bfloat16,
+                                             device=w.device)
             layer.int4_w = int4_w
 
     @property

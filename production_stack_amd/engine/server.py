@@ -1238,7 +1238,8 @@ def build_arg_parser() -> argparse.ArgumentParser:
                     choices=[None, "fp8", "int4"],
                     help="fp8 = OCP e4m3 weights through the fp8 MFMA pipe; "
                          "int4 = weight-only 4-bit (group 128, W4A16), "
-                         "bf16 activations, works with LoRA")
+                         "bf16 activations, works with LoRA; MoE experts "
+                         "included (natively fused with --moe-backend fused)")
     ap.add_argument("--fp8-gemm", default="scaled_mm",
                     choices=["scaled_mm", "native"],
                     help="with --quantization fp8: native = hand-written "

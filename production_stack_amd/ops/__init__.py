@@ -710,3 +710,78 @@ def int4_linear(x, packed, s, z) -> torch.Tensor:
     from production_stack_amd.ops import gemm_policy
 
     return gemm_policy.linear(x, int4_dequant(packed, s, z))
+
+
+def int4_quantize_experts(w: torch.Tensor):
+    """int4_quantize_weight of a stack of expert weights w [E, N, K], one
+    expert at a time so the fp32 temporaries stay at one expert's size:
+    (packed uint8 [E, N, K/2], s bf16 [E, N, K/128], z uint8 [E, N, K/128]).
+    Equal to int4_quantize_weight of the [E*N, K] view, reshaped."""
+    parts = [int4_quantize_weight(w[e]) for e in range(w.shape[0])]
+    return tuple(torch.stack(t) for t in zip(*parts))
+
+
+def fused_moe_int4_supported(
+    T: int, top_k: int, E: int, H: int, I: int
+) -> bool:
+    """The accept rule of csrc/moe_fused_w4.hip (ps_fused_moe_w4_supported):
+    fused_moe_supported with hidden/intermediate widths in whole 128-wide
+    quantization groups."""
+    return (
+        T >= 1 and 1 <= top_k <= E <= FUSED_MOE_MAX_EXPERTS
+        and T * top_k <= FUSED_MOE_MAX_PAIRS
+        and H >= INT4_GROUP and I >= INT4_GROUP
+        and H % INT4_GROUP == 0 and I % INT4_GROUP == 0
+    )
+
+
+def fused_moe_int4(
+    x: torch.Tensor,
+    gu: tuple,
+    dn: tuple,
+    topk_ids: torch.Tensor,
+    topk_weights: torch.Tensor,
+) -> torch.Tensor:
+    """fused_moe on int4 weight-only experts: gu = (packed [E, 2I, H/2],
+    s [E, 2I, H/128], z [E, 2I, H/128]) and dn = (packed [E, H, I/2],
+    s [E, H, I/128], z [E, H, I/128]) as int4_quantize_experts returns them.
+    On the GPU csrc/moe_fused_w4.hip dequantizes in registers to the bf16
+    values of int4_dequant; hipGraph-safe, bit-deterministic, and a token's
+    output row does not depend on the batch around it. Unsupported shapes
+    raise (see fused_moe_int4_supported). On the CPU: reference.fused_moe on
+    the dequantized stacks."""
+    if x.is_cuda:
+        _require_ext()
+        T, H = x.shape
+        top_k = topk_ids.shape[1]
+        E = dn[0].shape[0]
+        I = dn[0].shape[2] * 2
+        P = T * top_k
+        dev = x.device
+        if not fused_moe_int4_supported(T, top_k, E, H, I):
+            raise RuntimeError(
+                f"unsupported fused_moe_int4 shape T={T} top_k={top_k} "
+                f"E={E} H={H} I={I}"
+            )
+        S = _C.fused_moe_int4_splits(top_k, H, I)
+        # scratch via torch.empty so it lands in the graph pool under
+        # capture; the kernels overwrite every element they later read
+        out = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        sorted_pairs = torch.empty(P, dtype=torch.int32, device=dev)
+        act = torch.empty((P, I), dtype=torch.bfloat16, device=dev)
+        y = torch.empty((S, P, H), dtype=torch.float32, device=dev)
+        _C.fused_moe_int4(
+            out, offsets, sorted_pairs, act, y, x, *gu, *dn,
+            topk_ids.contiguous(), topk_weights.float().contiguous(),
+        )
+        return out
+
+    def deq(t):
+        p, s, z = t
+        return torch.stack(
+            [reference.int4_dequant(p[e], s[e], z[e])
+             for e in range(p.shape[0])]
+        )
+
+    return reference.fused_moe(x, deq(gu), deq(dn), topk_ids, topk_weights)

@@ -42,6 +42,7 @@ ext = CUDAExtension(
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
         "csrc/moe_fused.hip",
+        "csrc/moe_fused_w4.hip",
         "csrc/step_inputs.hip",
     ],
     extra_compile_args={
