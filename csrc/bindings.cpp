@@ -88,6 +88,11 @@ int ps_skinny_gemm_w4(void* out_bf16, void* ws, const void* x,
                       const void* packed, const void* scales,
                       const void* zeros, int M, int N, int K,
                       hipStream_t stream);
+int ps_gemm_w4_tiled_splits(int M, int N, int K);
+int ps_gemm_w4_tiled(void* out_bf16, void* ws, const void* x,
+                     const void* packed, const void* scales,
+                     const void* zeros, int M, int N, int K,
+                     hipStream_t stream);
 int ps_int4_dequant(void* out_bf16, const void* packed, const void* scales,
                     const void* zeros, long N, int K, hipStream_t stream);
 int ps_quant_fp8_rows(void* out_q, void* out_scale, const void* x, long T,
@@ -657,6 +662,36 @@ void skinny_gemm_w4(at::Tensor out, at::Tensor x, at::Tensor packed,
   TORCH_CHECK(rc == 0, "skinny w4 gemm launch failed");
 }
 
+// split_k = false forces one split (the bench tool's A/B of the depth rule)
+void gemm_w4_tiled(at::Tensor out, at::Tensor x, at::Tensor packed,
+                   at::Tensor s, at::Tensor z, bool split_k) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_BF16(x);
+  TORCH_CHECK(x.dim() == 2, "x must be [M, K]");
+  const auto nk = check_int4_weight(packed, s, z);
+  TORCH_CHECK(x.size(0) < (1L << 31), "unsupported tiled w4 gemm M=",
+              x.size(0));
+  const int M = (int)x.size(0);
+  const int N = (int)nk.first;
+  const int K = (int)nk.second;
+  TORCH_CHECK(x.size(1) == K, "K mismatch");
+  TORCH_CHECK(x.device() == packed.device() && out.device() == x.device(),
+              "out, x and the weight must be on one device");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "out must be [", M, ", ", N, "]");
+  const int splits = ps_gemm_w4_tiled_splits(M, N, K);
+  TORCH_CHECK(splits > 0, "unsupported tiled w4 gemm shape M=", M, " N=", N,
+              " K=", K);
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0,
+              "x rows must be 16-byte aligned");
+  at::Tensor ws;
+  void* ws_p = splitk_workspace(ws, x, split_k ? splits : 1, M, N);
+  int rc = ps_gemm_w4_tiled(out.data_ptr(), ws_p, x.data_ptr(),
+                            packed.data_ptr(), s.data_ptr(), z.data_ptr(), M,
+                            N, K, current_stream());
+  TORCH_CHECK(rc == 0, "tiled w4 gemm launch failed");
+}
+
 void int4_dequant(at::Tensor out, at::Tensor packed, at::Tensor s,
                   at::Tensor z) {
   CHECK_GPU_BF16(out);
@@ -1092,6 +1127,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(M<=256)");
   m.def("skinny_gemm_w4_splits", &ps_skinny_gemm_w4_splits,
         "Split-K depth skinny_gemm_w4 picks for (M, N, K); -1 if "
+        "unsupported");
+  m.def("gemm_w4_tiled", &gemm_w4_tiled,
+        "int4 weight-only (group 128) MFMA GEMM tiled 128 x 128, bf16 "
+        "activations, any M >= 1",
+        py::arg("out"), py::arg("x"), py::arg("packed"), py::arg("s"),
+        py::arg("z"), py::arg("split_k") = true);
+  m.def("gemm_w4_tiled_splits", &ps_gemm_w4_tiled_splits,
+        "Split-K depth gemm_w4_tiled picks for (M, N, K); -1 if "
         "unsupported");
   m.def("int4_dequant", &int4_dequant,
         "Packed int4 + group scales/zero points -> bf16 [N, K]");

@@ -16,6 +16,20 @@ in a decode step that walks a whole model.
 With --engine it also reports decode steps/s of an LLMEngine (--model) at
 each --batches value with quantization None and "int4".
 
+--tiled instead probes the prefill-sized kernel, csrc/gemm_w4_tiled.hip, on
+the same four shapes at M in {64, ..., 4096}. Per cell it times
+  tiled    ops.gemm_w4_tiled
+  tiled1   the same kernel with one split forced (A/B of the split-K rule)
+  dequant  ops.int4_dequant + gemm_policy.linear, what int4_linear runs
+           above M = 256 without the tiled backend
+  skinny   ops.skinny_gemm_w4, where M <= 256
+  bf16     gemm_policy.linear alone on a pre-dequantized weight: the floor
+           `dequant` cannot beat
+The candidates alternate within each of the --reps rounds, one window each;
+a window is sized to about 0.1 s of work from a calibration call. It prints
+the median us with the min..max spread, and tiled's TFLOP/s as 2*M*N*K over
+its median time.
+
 The driver starts one child process per GPU step, each under its own time
 limit, and stops at the first one that fails. --md FILE writes the results
 as markdown tables.
@@ -105,6 +119,108 @@ def worker_gemm(M, iters, reps):
         torch.cuda.empty_cache()
 
 
+TILED_MS = (64, 128, 256, 512, 1024, 2048, 4096)
+TILED_IMPLS = ("tiled", "tiled1", "dequant", "skinny", "bf16")
+
+
+def _time_alternating(cands, reps, window_s=0.1):
+    """{name: (median, min, max) us per call}: `reps` rounds, in each one
+    window per candidate in turn; fn(i) is call i of a candidate."""
+    import torch
+
+    def window(fn, iters):
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        for i in range(iters):
+            fn(i)
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) * 1e3 / iters
+
+    iters = {}
+    for name, fn in cands.items():
+        window(fn, 10)  # warm-up
+        per_call = window(fn, 10)
+        iters[name] = max(10, min(2000, int(window_s * 1e6 / per_call)))
+    out = {name: [] for name in cands}
+    for _ in range(reps):
+        for name, fn in cands.items():
+            out[name].append(window(fn, iters[name]))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in out.items()}
+
+
+def worker_tiled(M, reps):
+    import torch
+
+    from production_stack_amd import _C, ops
+    from production_stack_amd.ops import gemm_policy
+
+    assert torch.cuda.is_available() and ops.HAVE_EXT
+    for (N, K, name) in SHAPES:
+        torch.manual_seed(N * 1009 + K)
+        x = torch.randn(M, K, dtype=torch.bfloat16, device="cuda") / 8
+        # weight copies that together exceed the Infinity Cache, as above
+        n4 = 2 * CACHE_BYTES // _w4_bytes(N, K) + 1
+        n16 = 2 * CACHE_BYTES // (N * K * 2) + 1
+        w = torch.randn(N, K, dtype=torch.bfloat16, device="cuda") / 8
+        q = ops.int4_quantize_weight(w)
+        del w
+        q4 = [q] + [tuple(t.clone() for t in q) for _ in range(n4 - 1)]
+        wd = ops.int4_dequant(*q)
+        w16 = [wd] + [wd.clone() for _ in range(n16 - 1)]
+        out = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
+        cands = {
+            "tiled": lambda i: ops.gemm_w4_tiled(x, *q4[i % n4]),
+            "tiled1": lambda i: _C.gemm_w4_tiled(out, x, *q4[i % n4],
+                                                 split_k=False),
+            "dequant": lambda i: gemm_policy.linear(
+                x, ops.int4_dequant(*q4[i % n4])),
+            "bf16": lambda i: gemm_policy.linear(x, w16[i % n16]),
+        }
+        if M <= 256:
+            cands["skinny"] = lambda i: ops.skinny_gemm_w4(x, *q4[i % n4])
+        # same inputs, same answer, before anything is timed
+        want = gemm_policy.linear(x, wd).float()
+        cands["tiled1"](0)
+        for k, got in (("tiled", cands["tiled"](0)), ("tiled1", out)):
+            err = float((got.float() - want).abs().max() / want.abs().max())
+            assert err < 2.0 ** -6, (k, M, N, K, err)
+        cell = {"M": M, "N": N, "K": K, "name": name,
+                "splits": _C.gemm_w4_tiled_splits(M, N, K)}
+        for k, (med, lo, hi) in _time_alternating(cands, reps).items():
+            cell[k + "_us"] = round(med, 1)
+            cell[k + "_min_us"] = round(lo, 1)
+            cell[k + "_max_us"] = round(hi, 1)
+        cell["tiled_TFLOPs"] = round(
+            2 * M * N * K / cell["tiled_us"] / 1e6, 1)
+        print("TILED " + json.dumps(cell), flush=True)
+        del q4, w16, wd, q
+        torch.cuda.empty_cache()
+
+
+def _markdown_tiled(results):
+    out = ["| shape | M | splits | tiled us (min..max) | one split us | "
+           "dequant + bf16 us (min..max) | skinny w4 us | bf16 alone us | "
+           "tiled TFLOP/s | dequant / tiled |",
+           "|---|---|---|---|---|---|---|---|---|---|"]
+
+    def span(c, k):
+        if k + "_us" not in c:
+            return "-"
+        return f"{c[k + '_us']} ({c[k + '_min_us']}..{c[k + '_max_us']})"
+
+    for tag, c in results:
+        if tag != "TILED":
+            continue
+        out.append(
+            f"| {c['name']} {c['N']}x{c['K']} | {c['M']} | {c['splits']} | "
+            + " | ".join(span(c, k) for k in TILED_IMPLS)
+            + f" | {c['tiled_TFLOPs']} | "
+            f"{c['dequant_us'] / c['tiled_us']:.2f}x |")
+    return "\n".join(out) + "\n"
+
+
 def worker_engine(model, quant, batch, tokens):
     import time
 
@@ -163,7 +279,7 @@ def _child(args, limit, sink):
               "stopping", flush=True)
         sys.exit(1)
     for line in r.stdout.splitlines():
-        for tag in ("CELL ", "ENGINE "):
+        for tag in ("CELL ", "ENGINE ", "TILED "):
             if line.startswith(tag):
                 sink.append((tag.strip(), json.loads(line[len(tag):])))
 
@@ -209,7 +325,10 @@ def main():
                     help="seconds allowed to each child process")
     ap.add_argument("--md", default=None,
                     help="write the result tables to this markdown file")
-    ap.add_argument("--worker", choices=["gemm", "engine"])
+    ap.add_argument("--tiled", action="store_true",
+                    help="probe gemm_w4_tiled against the dequant path "
+                         "instead (M defaults to 64..4096)")
+    ap.add_argument("--worker", choices=["gemm", "engine", "tiled"])
     ap.add_argument("--m", type=int)
     ap.add_argument("--quant")
     ap.add_argument("--batch", type=int)
@@ -220,7 +339,18 @@ def main():
     if a.worker == "engine":
         worker_engine(a.model, a.quant, a.batch, a.tokens)
         return
+    if a.worker == "tiled":
+        worker_tiled(a.m, a.reps)
+        return
     results = []
+    if a.tiled:
+        for M in (a.ms if a.ms != list(MS) else TILED_MS):
+            _child(["--worker", "tiled", "--m", str(M), "--reps",
+                    str(a.reps)], a.step_timeout, results)
+        if a.md:
+            with open(a.md, "w") as f:
+                f.write(_markdown_tiled(results))
+        return
     for M in a.ms:
         _child(["--worker", "gemm", "--m", str(M), "--iters", str(a.iters),
                 "--reps", str(a.reps)], a.step_timeout, results)

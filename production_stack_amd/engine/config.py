@@ -394,6 +394,12 @@ class EngineConfig:
     # with per-row activation and per-channel weight scales for steps of up
     # to 256 tokens; larger steps fall through to _scaled_mm)
     fp8_gemm: str = "scaled_mm"
+    # int4 GEMM backend for steps above skinny_gemm_w4's 256 tokens, read
+    # only when quantization == "int4": "dequant" (int4_dequant into a
+    # transient bf16 weight + the bf16 GEMM dispatch) or "tiled"
+    # (csrc/gemm_w4_tiled.hip, no bf16 weight is materialised). Steps of up
+    # to 256 tokens run skinny_gemm_w4 under both.
+    int4_gemm: str = "dequant"
     # sparse-MoE expert dispatch: "loop" (per-expert Python loop over
     # hipBLASLt GEMMs; host syncs, so no decode hipGraphs) or "fused"
     # (csrc/moe_fused.hip grouped kernels, csrc/moe_fused_w4.hip on int4

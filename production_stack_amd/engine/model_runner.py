@@ -92,7 +92,14 @@ class ModelRunner:
                 f"unknown quantization {config.quantization!r}; "
                 "expected None, 'fp8' or 'int4'"
             )
+        if config.int4_gemm not in ("dequant", "tiled"):
+            raise ValueError(
+                f"unknown int4_gemm {config.int4_gemm!r}; "
+                "expected 'dequant' or 'tiled'"
+            )
         if config.quantization == "int4":
+            for layer in self.model.layers:
+                layer.int4_gemm = config.int4_gemm
             self.model.quantize_int4()
         if config.quantization == "fp8":
             for layer in self.model.layers:

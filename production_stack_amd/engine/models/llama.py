@@ -179,6 +179,8 @@ class LlamaLayer(nn.Module):
         # int4 weight-only projections (quantize_int4): activations stay
         # bf16, so only the four GEMM calls below change
         int4 = getattr(self, "int4_w", None) or {}
+        # steps above skinny_gemm_w4's M range: "dequant" or "tiled"
+        int4_gemm = getattr(self, "int4_gemm", "dequant")
         # fused act-quant path: (add-)RMSNorm emits fp8 + row scales
         # directly, skipping the bf16 round trip;
         # LoRA needs the bf16 normed activations, so it keeps the plain
@@ -214,7 +216,8 @@ class LlamaLayer(nn.Module):
             if fp8 is not None:
                 qkv = ops.fp8_linear(hidden, *fp8["qkv"])
             elif "qkv" in int4:
-                qkv = ops.int4_linear(hidden, *int4["qkv"])
+                qkv = ops.int4_linear(hidden, *int4["qkv"],
+                                      backend=int4_gemm)
             else:
                 qkv = gemm_policy.linear(hidden, self.qkv_proj)
         if self.qkv_bias is not None:
@@ -335,7 +338,8 @@ class LlamaLayer(nn.Module):
             attn_out = ops.fp8_linear(attn.reshape(T, qs),
                                       *self.fp8_w["o"])
         elif "o" in int4:
-            attn_out = ops.int4_linear(attn.reshape(T, qs), *int4["o"])
+            attn_out = ops.int4_linear(attn.reshape(T, qs), *int4["o"],
+                                       backend=int4_gemm)
         else:
             attn_out = gemm_policy.linear(attn.view(T, qs), self.o_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -369,7 +373,8 @@ class LlamaLayer(nn.Module):
             if fp8 is not None:
                 gate_up = ops.fp8_linear(hidden, *fp8["gate_up"])
             elif "gate_up" in int4:
-                gate_up = ops.int4_linear(hidden, *int4["gate_up"])
+                gate_up = ops.int4_linear(hidden, *int4["gate_up"],
+                                          backend=int4_gemm)
             else:
                 gate_up = gemm_policy.linear(hidden, self.gate_up_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -396,7 +401,8 @@ class LlamaLayer(nn.Module):
             if fp8 is not None:
                 mlp_out = ops.fp8_linear(act, *fp8["down"])
             elif "down" in int4:
-                mlp_out = ops.int4_linear(act, *int4["down"])
+                mlp_out = ops.int4_linear(act, *int4["down"],
+                                          backend=int4_gemm)
             else:
                 mlp_out = gemm_policy.linear(act, self.down_proj)
         if slots is not None and meta.lora_idx is not None:
@@ -431,11 +437,15 @@ class LlamaLayer(nn.Module):
                 # csrc/moe_fused_w4.hip; larger steps keep the loop below
                 return ops.fused_moe_int4(x, gu, dn, sel, weights)
 
+            int4_gemm = getattr(self, "int4_gemm", "dequant")
+
             def gate_up_of(xe, e):
-                return ops.int4_linear(xe, gu[0][e], gu[1][e], gu[2][e])
+                return ops.int4_linear(xe, gu[0][e], gu[1][e], gu[2][e],
+                                       backend=int4_gemm)
 
             def down_of(act, e):
-                return ops.int4_linear(act, dn[0][e], dn[1][e], dn[2][e])
+                return ops.int4_linear(act, dn[0][e], dn[1][e], dn[2][e],
+                                       backend=int4_gemm)
         else:
             if (
                 self.moe_backend == "fused"

@@ -1245,6 +1245,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
                     help="with --quantization fp8: native = hand-written "
                          "fp8 MFMA GEMM with row/channel scales for steps "
                          "of up to 256 tokens")
+    ap.add_argument("--int4-gemm", default="dequant",
+                    choices=["dequant", "tiled"],
+                    help="with --quantization int4, for steps of more than "
+                         "256 tokens: tiled = hand-written tiled int4 MFMA "
+                         "GEMM, no transient bf16 copy of the weights")
     ap.add_argument("--moe-backend", default="loop",
                     choices=["loop", "fused"],
                     help="fused = grouped MoE expert kernels + decode "
@@ -1319,6 +1324,7 @@ def main() -> None:
         speculative_weights_path=args.speculative_weights_path,
         quantization=args.quantization,
         fp8_gemm=args.fp8_gemm,
+        int4_gemm=args.int4_gemm,
         moe_backend=args.moe_backend,
         enable_lora=args.enable_lora,
         max_loras=args.max_loras,

@@ -698,15 +698,62 @@ def skinny_gemm_w4(x, packed, s, z) -> torch.Tensor:
     return out
 
 
-def int4_linear(x, packed, s, z) -> torch.Tensor:
-    """x @ W_deq^T for an int4 weight: the native kernel when x is on the
-    GPU and skinny_gemm_w4_supported(M, N, K) holds; otherwise (prefill
-    chunks with M > 256) int4_dequant into a transient bf16 buffer and the
-    bf16 GEMM dispatch; the reference on the CPU."""
+def gemm_w4_tiled_supported(M: int, N: int, K: int) -> bool:
+    """The accept rule of csrc/gemm_w4_tiled.hip
+    (ps_gemm_w4_tiled_splits > 0): any M >= 1, 64-aligned N, K in whole
+    128-wide quantization groups, i.e. every weight quantize_int4
+    produces."""
+    return (
+        M >= 1 and N >= 64 and K >= INT4_GROUP
+        and N % 64 == 0 and K % INT4_GROUP == 0
+    )
+
+
+def gemm_w4_tiled(x, packed, s, z) -> torch.Tensor:
+    """out[M,N] bf16 = x[M,K] bf16 @ W_deq[N,K]^T through the 128 x 128
+    tiled int4 MFMA kernel (csrc/gemm_w4_tiled.hip), for prefill-sized M:
+    each weight tile is dequantized once per workgroup into LDS, to the bf16
+    values of int4_dequant, with fp32 accumulation; no bf16 copy of the
+    weight is written to memory. Bit-deterministic for a fixed (M, N, K);
+    the split-K depth depends on the tile count, so unlike skinny_gemm_w4 a
+    row's bits may depend on M. GPU only; shapes outside
+    gemm_w4_tiled_supported raise. M == 0 returns an empty [0, N]."""
+    _require_ext()
+    out = torch.empty(
+        (x.shape[0], packed.shape[0]), dtype=torch.bfloat16, device=x.device
+    )
+    if x.shape[0] == 0:
+        return out
+    _C.gemm_w4_tiled(out, x, packed, s, z)
+    return out
+
+
+# First M that int4_linear(backend="tiled") sends to gemm_w4_tiled; below it
+# skinny_gemm_w4 keeps decode steps bit-for-bit independent of the batch.
+INT4_TILED_MIN_M = 257
+INT4_GEMM_BACKENDS = ("dequant", "tiled")
+
+
+def int4_linear(x, packed, s, z, backend: str = "dequant") -> torch.Tensor:
+    """x @ W_deq^T for an int4 weight: skinny_gemm_w4 when x is on the GPU
+    and skinny_gemm_w4_supported(M, N, K) holds (M <= 256). Larger M (prefill
+    chunks) depends on `backend`: "tiled" runs gemm_w4_tiled where
+    gemm_w4_tiled_supported accepts the shape; "dequant", and any shape
+    neither kernel takes, runs int4_dequant into a transient bf16 buffer and
+    the bf16 GEMM dispatch. The reference on the CPU."""
+    if backend not in INT4_GEMM_BACKENDS:
+        raise ValueError(
+            f"unknown int4 GEMM backend {backend!r}; expected one of "
+            f"{INT4_GEMM_BACKENDS}"
+        )
     if not x.is_cuda:
         return reference.int4_linear(x, packed, s, z)
-    if skinny_gemm_w4_supported(x.shape[0], packed.shape[0], x.shape[1]):
+    M, N, K = x.shape[0], packed.shape[0], x.shape[1]
+    if skinny_gemm_w4_supported(M, N, K):
         return skinny_gemm_w4(x, packed, s, z)
+    if (backend == "tiled" and M >= INT4_TILED_MIN_M
+            and gemm_w4_tiled_supported(M, N, K)):
+        return gemm_w4_tiled(x, packed, s, z)
     from production_stack_amd.ops import gemm_policy
 
     return gemm_policy.linear(x, int4_dequant(packed, s, z))
