@@ -88,6 +88,10 @@ int ps_skinny_gemm_w4(void* out_bf16, void* ws, const void* x,
                       const void* packed, const void* scales,
                       const void* zeros, int M, int N, int K,
                       hipStream_t stream);
+int ps_gemm_fp8_tiled_splits(int M, int N, int K);
+int ps_gemm_fp8_tiled(void* out_bf16, void* ws, const void* xq,
+                      const void* sx, const void* wq, const void* sw, int M,
+                      int N, int K, hipStream_t stream);
 int ps_gemm_w4_tiled_splits(int M, int N, int K);
 int ps_gemm_w4_tiled(void* out_bf16, void* ws, const void* x,
                      const void* packed, const void* scales,
@@ -606,6 +610,43 @@ void skinny_gemm_fp8(at::Tensor out, at::Tensor xq, at::Tensor sx,
                               sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), M,
                               N, K, current_stream());
   TORCH_CHECK(rc == 0, "skinny fp8 gemm launch failed");
+}
+
+void gemm_fp8_tiled(at::Tensor out, at::Tensor xq, at::Tensor sx,
+                    at::Tensor wq, at::Tensor sw) {
+  CHECK_GPU_BF16(out);
+  CHECK_GPU_DTYPE(xq, at::kFloat8_e4m3fn);
+  CHECK_GPU_DTYPE(wq, at::kFloat8_e4m3fn);
+  CHECK_GPU_DTYPE(sx, at::kFloat);
+  CHECK_GPU_DTYPE(sw, at::kFloat);
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2, "xq and wq must be 2D");
+  TORCH_CHECK(xq.size(0) < (1L << 31), "unsupported tiled fp8 gemm M=",
+              xq.size(0));
+  const int M = (int)xq.size(0);
+  const int K = (int)xq.size(1);
+  const int N = (int)wq.size(0);
+  TORCH_CHECK(wq.size(1) == K, "K mismatch");
+  TORCH_CHECK(sx.numel() == M, "sx must hold one scale per row of xq");
+  TORCH_CHECK(sw.numel() == N, "sw must hold one scale per row of wq");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N,
+              "out must be [", M, ", ", N, "]");
+  TORCH_CHECK(xq.device() == wq.device() && sx.device() == xq.device() &&
+                  sw.device() == xq.device() && out.device() == xq.device(),
+              "out, xq, sx, wq and sw must be on one device");
+  const int splits = ps_gemm_fp8_tiled_splits(M, N, K);
+  TORCH_CHECK(splits > 0, "unsupported tiled fp8 gemm shape M=", M, " N=", N,
+              " K=", K);
+  // rows are read as 16-byte vectors; K % 64 == 0 keeps every row start
+  // aligned once the base is
+  TORCH_CHECK((uintptr_t)xq.data_ptr() % 16 == 0 &&
+                  (uintptr_t)wq.data_ptr() % 16 == 0,
+              "xq and wq rows must be 16-byte aligned");
+  at::Tensor ws;
+  void* ws_p = splitk_workspace(ws, xq, splits, M, N);
+  int rc = ps_gemm_fp8_tiled(out.data_ptr(), ws_p, xq.data_ptr(),
+                             sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), M,
+                             N, K, current_stream());
+  TORCH_CHECK(rc == 0, "tiled fp8 gemm launch failed");
 }
 
 // packed [N, K/2] uint8, s [N, K/128] bf16, z [N, K/128] uint8 of one int4
@@ -1127,6 +1168,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(M<=256)");
   m.def("skinny_gemm_w4_splits", &ps_skinny_gemm_w4_splits,
         "Split-K depth skinny_gemm_w4 picks for (M, N, K); -1 if "
+        "unsupported");
+  m.def("gemm_fp8_tiled", &gemm_fp8_tiled,
+        "fp8 e4m3 128x128-tiled MFMA GEMM with row/channel scales (any M)");
+  m.def("gemm_fp8_tiled_splits", &ps_gemm_fp8_tiled_splits,
+        "Split-K depth gemm_fp8_tiled picks for (M, N, K); -1 if "
         "unsupported");
   m.def("gemm_w4_tiled", &gemm_w4_tiled,
         "int4 weight-only (group 128) MFMA GEMM tiled 128 x 128, bf16 "

@@ -39,8 +39,9 @@
 // XOR.
 //
 // The K-range, lane coordinates, epilogue, combine loop and launch ladder are
-// csrc/skinny_common.h's; the split depth is csrc/splitk.h's.
-#include "skinny_common.h"
+// csrc/skinny_common.h's; the split depth is csrc/splitk.h's; the scale
+// functor and the combine kernel are csrc/fp8_common.h's.
+#include "fp8_common.h"
 
 typedef __attribute__((ext_vector_type(2))) long ps_f8x16;  // 16 fp8, 16 B
 
@@ -119,23 +120,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_fp8_kernel(
   PS_SKINNY_EPILOGUE(v * (sx[m] * swn));
 }
 
-struct ps_f8_scale {
-  const float* sx;  // [M]
-  const float* sw;  // [N]
-  int N;
-  PS_DEV float operator()(float acc, long i) const {
-    return acc * (sx[i / N] * sw[i % N]);
-  }
-};
-
-__global__ __launch_bounds__(256) void skinny_fp8_combine_kernel(
-    unsigned short* __restrict__ out,  // [M, N] bf16
-    const float* __restrict__ ws,      // [S, M, N] fp32, unscaled
-    const float* __restrict__ sx, const float* __restrict__ sw, long MN,
-    int N, int splits) {
-  ps_splitk_combine(out, ws, MN, splits, ps_f8_scale{sx, sw, N});
-}
-
 extern "C" {
 
 // Split depth for a shape, a function of (N, K) only; -1 if unsupported.
@@ -161,12 +145,8 @@ int ps_skinny_gemm_fp8(void* out_bf16, void* ws, const void* xq,
       (const float*)sx, (const unsigned char*)wq, (const float*)sw, M, N, K)
   PS_SKINNY_M_LADDER(M, PS_SGF);
 #undef PS_SGF
-  if (splits > 1) {
-    const long MN = (long)M * N;
-    skinny_fp8_combine_kernel<<<dim3((MN + 255) / 256), 256, 0, stream>>>(
-        (unsigned short*)out_bf16, (const float*)ws, (const float*)sx,
-        (const float*)sw, MN, N, splits);
-  }
+  if (splits > 1)
+    ps_launch_fp8_combine(out_bf16, ws, sx, sw, M, N, splits, stream);
   return 0;
 }
 

@@ -17,12 +17,27 @@ in a decode step that walks a whole model.
 With --engine it also reports decode steps/s of an engine (mini-llama, or
 --model llama-3-8b) under fp8_gemm=scaled_mm and fp8_gemm=native.
 
+--tiled instead probes the prefill-sized kernel, csrc/gemm_fp8_tiled.hip, on
+the same four shapes at M in {512, 1024, 2048, 4096}. Per cell it times, in
+one process,
+  tiled    ops.gemm_fp8_tiled
+  scaledmm ops.fp8_linear_rowwise(backend="scaled_mm") on the same operands,
+           what these steps run without the tiled backend
+  bf16     gemm_policy.linear on a bf16 weight of the same shape
+after checking tiled against scaledmm. The candidates alternate within each
+of the --reps rounds, one window each; a window is sized to about 0.1 s of
+work from a calibration call, and each call uses the next of several weight
+copies that together exceed the Infinity Cache. It prints the median us with
+the min..max spread, and each candidate's TFLOP/s as 2*M*N*K over its median
+time. --md FILE writes the table as markdown.
+
 The driver starts one child process per GPU step, each under its own time
 limit, and stops at the first one that fails.
 """
 import argparse
 import json
 import os
+import statistics
 import subprocess
 import sys
 
@@ -98,6 +113,95 @@ def worker_gemm(M, iters):
     return rows
 
 
+TILED_MS = (512, 1024, 2048, 4096)
+TILED_IMPLS = ("tiled", "scaledmm", "bf16")
+
+
+def _time_alternating(cands, reps, window_s=0.1):
+    """{name: (median, min, max) us per call}: `reps` rounds, in each one
+    window per candidate in turn; fn(i) is call i of a candidate."""
+    import torch
+
+    def window(fn, iters):
+        start = torch.cuda.Event(enable_timing=True)
+        stop = torch.cuda.Event(enable_timing=True)
+        start.record()
+        for i in range(iters):
+            fn(i)
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop) * 1e3 / iters
+
+    iters = {}
+    for name, fn in cands.items():
+        window(fn, 10)  # warm-up
+        per_call = window(fn, 10)
+        iters[name] = max(10, min(2000, int(window_s * 1e6 / per_call)))
+    out = {name: [] for name in cands}
+    for _ in range(reps):
+        for name, fn in cands.items():
+            out[name].append(window(fn, iters[name]))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in out.items()}
+
+
+def worker_tiled(M, reps):
+    import torch
+
+    from production_stack_amd import _C, ops
+    from production_stack_amd.ops import gemm_policy
+
+    assert torch.cuda.is_available() and ops.HAVE_EXT
+    for (N, K, name) in SHAPES:
+        torch.manual_seed(N * 1009 + K)
+        x = torch.randn(M, K, dtype=torch.bfloat16, device="cuda") / 8
+        xq, sx = ops.quant_fp8_rows(x)
+        n8 = 2 * CACHE_BYTES // (N * K) + 1
+        n16 = 2 * CACHE_BYTES // (N * K * 2) + 1
+        w = torch.randn(N, K, dtype=torch.bfloat16, device="cuda") / 8
+        wq, sw = ops.fp8_quantize_weight_rowwise(w)
+        # further copies: the bytes matter, not the values
+        q8 = [wq] + [wq.clone() for _ in range(n8 - 1)]
+        w16 = [w] + [w.clone() for _ in range(n16 - 1)]
+        cands = {
+            "tiled": lambda i: ops.gemm_fp8_tiled(xq, sx, q8[i % n8], sw),
+            "scaledmm": lambda i: ops.fp8_linear_rowwise(
+                xq, sx, q8[i % n8], sw, backend="scaled_mm"),
+            "bf16": lambda i: gemm_policy.linear(x, w16[i % n16]),
+        }
+        # same inputs, same answer, before anything is timed
+        want = cands["scaledmm"](0).float()
+        got = cands["tiled"](0).float()
+        err = float((got - want).abs().max() / want.abs().max())
+        assert err < 2.0 ** -6, (M, N, K, err)
+        cell = {"M": M, "N": N, "K": K, "name": name,
+                "splits": _C.gemm_fp8_tiled_splits(M, N, K)}
+        for k, (med, lo, hi) in _time_alternating(cands, reps).items():
+            cell[k + "_us"] = round(med, 1)
+            cell[k + "_min_us"] = round(lo, 1)
+            cell[k + "_max_us"] = round(hi, 1)
+            cell[k + "_TFLOPs"] = round(2 * M * N * K / med / 1e6, 1)
+        print("TILED " + json.dumps(cell), flush=True)
+        del q8, w16, w, wq
+        torch.cuda.empty_cache()
+
+
+def _markdown_tiled(cells):
+    out = ["| shape | M | splits | tiled us (min..max) | scaled_mm path us "
+           "(min..max) | bf16 us (min..max) | tiled TFLOP/s | scaled_mm / "
+           "tiled | bf16 / tiled |",
+           "|---|---|---|---|---|---|---|---|---|"]
+    for c in cells:
+        out.append(
+            f"| {c['name']} {c['N']}x{c['K']} | {c['M']} | {c['splits']} | "
+            + " | ".join(
+                f"{c[k + '_us']} ({c[k + '_min_us']}..{c[k + '_max_us']})"
+                for k in TILED_IMPLS)
+            + f" | {c['tiled_TFLOPs']} | "
+            f"{c['scaledmm_us'] / c['tiled_us']:.2f}x | "
+            f"{c['bf16_us'] / c['tiled_us']:.2f}x |")
+    return "\n".join(out) + "\n"
+
+
 def worker_engine(model, backend, batch, tokens):
     import time
 
@@ -142,14 +246,19 @@ def worker_engine(model, backend, batch, tokens):
     print("ENGINE " + json.dumps(res), flush=True)
 
 
-def _child(args, limit):
+def _child(args, limit, sink=None):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable,
            os.path.abspath(__file__)] + args
-    r = subprocess.run(cmd, cwd=ROOT)
+    r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, text=True)
+    sys.stdout.write(r.stdout)
+    sys.stdout.flush()
     if r.returncode != 0:
         print(f"step {' '.join(args)} ended with status {r.returncode}; "
               "stopping", flush=True)
         sys.exit(1)
+    if sink is not None:
+        sink += [json.loads(line[6:]) for line in r.stdout.splitlines()
+                 if line.startswith("TILED ")]
 
 
 def main():
@@ -164,7 +273,14 @@ def main():
     ap.add_argument("--tokens", type=int, default=136)
     ap.add_argument("--step-timeout", type=int, default=150,
                     help="seconds allowed to each child process")
-    ap.add_argument("--worker", choices=["gemm", "engine"])
+    ap.add_argument("--tiled", action="store_true",
+                    help="probe gemm_fp8_tiled against the scaled_mm path "
+                         "and bf16 instead (M defaults to 512..4096)")
+    ap.add_argument("--reps", type=int, default=5,
+                    help="--tiled: rounds of alternating timed windows")
+    ap.add_argument("--md", default=None,
+                    help="--tiled: write the table to this markdown file")
+    ap.add_argument("--worker", choices=["gemm", "engine", "tiled"])
     ap.add_argument("--m", type=int)
     ap.add_argument("--backend")
     a = ap.parse_args()
@@ -173,6 +289,18 @@ def main():
         return
     if a.worker == "engine":
         worker_engine(a.model, a.backend, a.batch, a.tokens)
+        return
+    if a.worker == "tiled":
+        worker_tiled(a.m, a.reps)
+        return
+    if a.tiled:
+        cells = []
+        for M in (a.ms if a.ms != list(MS) else TILED_MS):
+            _child(["--worker", "tiled", "--m", str(M), "--reps",
+                    str(a.reps)], a.step_timeout, cells)
+        if a.md:
+            with open(a.md, "w") as f:
+                f.write(_markdown_tiled(cells))
         return
     for M in a.ms:
         _child(["--worker", "gemm", "--m", str(M), "--iters", str(a.iters)],

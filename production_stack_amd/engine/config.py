@@ -390,9 +390,11 @@ class EngineConfig:
     # at engine start.
     quantization: Optional[str] = None
     # fp8 GEMM backend, read only when quantization == "fp8": "scaled_mm"
-    # (torch._scaled_mm / hipBLASLt) or "native" (csrc/skinny_gemm_fp8.hip
+    # (torch._scaled_mm / hipBLASLt), "native" (csrc/skinny_gemm_fp8.hip
     # with per-row activation and per-channel weight scales for steps of up
-    # to 256 tokens; larger steps fall through to _scaled_mm)
+    # to 256 tokens; larger steps fall through to _scaled_mm) or
+    # "native_tiled" ("native" plus csrc/gemm_fp8_tiled.hip with the same
+    # scales for larger steps, so prefill chunks stay in HIP too)
     fp8_gemm: str = "scaled_mm"
     # int4 GEMM backend for steps above skinny_gemm_w4's 256 tokens, read
     # only when quantization == "int4": "dequant" (int4_dequant into a

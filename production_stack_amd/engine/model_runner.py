@@ -82,10 +82,10 @@ class ModelRunner:
             self.model.lora_slots = self.lora_slots
             for layer in self.model.layers:
                 layer.lora_slots = self.lora_slots
-        if config.fp8_gemm not in ("scaled_mm", "native"):
+        if config.fp8_gemm not in ("scaled_mm", "native", "native_tiled"):
             raise ValueError(
                 f"unknown fp8_gemm {config.fp8_gemm!r}; "
-                "expected 'scaled_mm' or 'native'"
+                "expected 'scaled_mm', 'native' or 'native_tiled'"
             )
         if config.quantization not in (None, "fp8", "int4"):
             raise ValueError(

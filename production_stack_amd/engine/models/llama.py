@@ -186,12 +186,14 @@ class LlamaLayer(nn.Module):
         # LoRA needs the bf16 normed activations, so it keeps the plain
         # norm + per-tensor fp8 GEMM path.
         # fp8_gemm == "native" runs the rowwise GEMMs in
-        # csrc/skinny_gemm_fp8.hip, so it takes this path whether or not
+        # csrc/skinny_gemm_fp8.hip ("native_tiled": and, above 256 tokens,
+        # in csrc/gemm_fp8_tiled.hip), so it takes this path whether or not
         # _scaled_mm accepts rowwise scales.
         backend = getattr(self, "fp8_gemm", "scaled_mm")
+        native = backend in ("native", "native_tiled")
         fuse_q = (fp8 is not None and hidden.is_cuda
                   and meta.lora_idx is None and not meta.lora_groups
-                  and (backend == "native"
+                  and (native
                        or ops.fp8_rowwise_supported(hidden.device)))
         if fuse_q:
             if residual is None:
@@ -329,7 +331,7 @@ class LlamaLayer(nn.Module):
             attn = buf
         else:
             attn = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
-        if fuse_q and backend == "native":
+        if fuse_q and native:
             # nothing upstream can emit the attention output quantized
             aq, sa = ops.quant_fp8_rows(attn.view(T, qs))
             attn_out = ops.fp8_linear_rowwise(aq, sa, *fp8["o"],
@@ -551,8 +553,8 @@ class LlamaForCausalLM(nn.Module):
         halves
         weight HBM and runs GEMMs through the fp8 MFMA pipe. Embedding,
         lm_head and norms stay bf16. Scales are per output channel when
-        the layer's fp8_gemm is "native" or _scaled_mm takes rowwise
-        scales, per tensor otherwise."""
+        the layer's fp8_gemm is "native" or "native_tiled", or _scaled_mm
+        takes rowwise scales, per tensor otherwise."""
         for layer in self.layers:
             fp8_w = {}
             proj_names = [("qkv", "qkv_proj"), ("o", "o_proj")]
@@ -561,7 +563,8 @@ class LlamaForCausalLM(nn.Module):
                                ("down", "down_proj")]
             for key, pname in proj_names:
                 w = getattr(layer, pname)
-                if (getattr(layer, "fp8_gemm", "scaled_mm") == "native"
+                if (getattr(layer, "fp8_gemm", "scaled_mm")
+                        in ("native", "native_tiled")
                         or (w.is_cuda
                             and ops.fp8_rowwise_supported(w.device))):
                     w_q, scale = ops.fp8_quantize_weight_rowwise(w.data)

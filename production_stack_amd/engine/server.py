@@ -1241,10 +1241,11 @@ def build_arg_parser() -> argparse.ArgumentParser:
                          "bf16 activations, works with LoRA; MoE experts "
                          "included (natively fused with --moe-backend fused)")
     ap.add_argument("--fp8-gemm", default="scaled_mm",
-                    choices=["scaled_mm", "native"],
+                    choices=["scaled_mm", "native", "native_tiled"],
                     help="with --quantization fp8: native = hand-written "
                          "fp8 MFMA GEMM with row/channel scales for steps "
-                         "of up to 256 tokens")
+                         "of up to 256 tokens; native_tiled = the same plus "
+                         "a hand-written tiled fp8 GEMM for larger steps")
     ap.add_argument("--int4-gemm", default="dequant",
                     choices=["dequant", "tiled"],
                     help="with --quantization int4, for steps of more than "

@@ -591,6 +591,39 @@ def skinny_gemm_fp8(xq, sx, wq, sw) -> torch.Tensor:
     return out
 
 
+def gemm_fp8_tiled_supported(M: int, N: int, K: int) -> bool:
+    """The accept rule of csrc/gemm_fp8_tiled.hip
+    (ps_gemm_fp8_tiled_splits > 0): skinny_gemm_fp8's without the cap on M,
+    so every weight the decode kernel serves is served at every M >= 1."""
+    return M >= 1 and N >= 64 and K >= 64 and N % 64 == 0 and K % 64 == 0
+
+
+def gemm_fp8_tiled(xq, sx, wq, sw) -> torch.Tensor:
+    """out[M,N] bf16 = (xq*sx[:,None]) @ (wq*sw[:,None]).T through the
+    128 x 128 tiled fp8 MFMA kernel (csrc/gemm_fp8_tiled.hip), for
+    prefill-sized M: operands and numerics as skinny_gemm_fp8 (fp32
+    accumulation, scales applied once before the bf16 round, no fp32 [M, N]
+    intermediate). Bit-deterministic for a fixed (M, N, K); the split-K
+    depth depends on the tile count, so unlike skinny_gemm_fp8 a row's bits
+    may depend on M. GPU only; shapes outside gemm_fp8_tiled_supported
+    raise. M == 0 returns an empty [0, N]."""
+    _require_ext()
+    out = torch.empty(
+        (xq.shape[0], wq.shape[0]), dtype=torch.bfloat16, device=xq.device
+    )
+    if xq.shape[0] == 0:
+        return out
+    _C.gemm_fp8_tiled(out, xq, sx, wq, sw)
+    return out
+
+
+# First M that fp8_linear_rowwise(backend="native_tiled") sends to
+# gemm_fp8_tiled; below it skinny_gemm_fp8 keeps decode steps bit-for-bit
+# independent of the batch.
+FP8_TILED_MIN_M = 257
+FP8_GEMM_BACKENDS = ("scaled_mm", "native", "native_tiled")
+
+
 def quant_fp8_rows(x: torch.Tensor):
     """Per-row dynamic fp8 quantization of a bf16 [T, D] matrix (rows may
     be strided): returns (xq e4m3 [T, D], sx fp32 [T]) with
@@ -616,17 +649,23 @@ def fp8_linear_rowwise(xq, sx, w_q, sw, backend="scaled_mm"):
     backend="native" runs skinny_gemm_fp8 instead when the input is on the
     GPU and skinny_gemm_fp8_supported(M, N, K) holds. Everything else
     (prefill chunks with M > 256, shard shapes that are not 64-aligned)
-    falls through to the _scaled_mm path above, unchanged."""
-    if backend not in ("scaled_mm", "native"):
+    falls through to the _scaled_mm path above, unchanged.
+
+    backend="native_tiled" does the same up to M = 256 and runs
+    gemm_fp8_tiled for M >= FP8_TILED_MIN_M where gemm_fp8_tiled_supported
+    holds, so only shapes neither kernel takes reach _scaled_mm."""
+    if backend not in FP8_GEMM_BACKENDS:
         raise ValueError(
             f"unknown fp8 gemm backend {backend!r}; "
-            "expected 'scaled_mm' or 'native'"
+            f"expected one of {FP8_GEMM_BACKENDS}"
         )
-    if (
-        backend == "native" and xq.is_cuda
-        and skinny_gemm_fp8_supported(xq.shape[0], w_q.shape[0], xq.shape[1])
-    ):
-        return skinny_gemm_fp8(xq, sx, w_q, sw)
+    if backend != "scaled_mm" and xq.is_cuda:
+        M, N, K = xq.shape[0], w_q.shape[0], xq.shape[1]
+        if skinny_gemm_fp8_supported(M, N, K):
+            return skinny_gemm_fp8(xq, sx, w_q, sw)
+        if (backend == "native_tiled" and M >= FP8_TILED_MIN_M
+                and gemm_fp8_tiled_supported(M, N, K)):
+            return gemm_fp8_tiled(xq, sx, w_q, sw)
     if fp8_rowwise_supported(xq.device):
         return torch._scaled_mm(
             xq, w_q.t(), scale_a=sx[:, None].contiguous(),

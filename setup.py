@@ -39,6 +39,7 @@ ext = CUDAExtension(
         "csrc/skinny_gemm_fp8.hip",
         "csrc/skinny_gemm_w4.hip",
         "csrc/gemm_w4_tiled.hip",
+        "csrc/gemm_fp8_tiled.hip",
         "csrc/gemm8p.hip",
         "csrc/cachegen.cpp",
         "csrc/lora_bgmv.hip",
