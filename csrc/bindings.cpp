@@ -9,6 +9,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "step_pack.h"
@@ -72,6 +73,9 @@ void ps_reshape_and_cache(const void* k, const void* v, void* k_cache,
                           hipStream_t stream);
 void ps_greedy_sample(void* out, const void* logits, long R, int V,
                       hipStream_t stream);
+// non-zero, launching nothing, when R < 1 or V < 1
+int ps_sample(void* out, void* u_out, const void* logits, const void* params,
+              const void* u_in, long R, int V, hipStream_t stream);
 void ps_kv_quant(void* out, void* scales, const void* in, long rows, int hd,
                  hipStream_t stream);
 void ps_kv_dequant(void* out, const void* in, const void* scales, long rows,
@@ -1004,6 +1008,64 @@ void greedy_sample(at::Tensor out, at::Tensor logits) {
   ps_greedy_sample(out.data_ptr(), logits.data_ptr(), R, V, current_stream());
 }
 
+// The host copy of the [R, 8] int32 sampling records (temperature, top_k,
+// top_p, min_p, key, counter): the ranges the kernel relies on.
+void sample_check(at::Tensor params) {
+  TORCH_CHECK(params.device().is_cpu() && params.scalar_type() == at::kInt &&
+                  params.is_contiguous() && params.dim() == 2 &&
+                  params.size(1) == 8,
+              "sample params must be a contiguous CPU int32 [R, 8] tensor");
+  const long R = params.size(0);
+  const int* p = params.data_ptr<int>();
+  for (long r = 0; r < R; r++) {
+    float t, top_p, min_p;
+    memcpy(&t, p + r * 8, 4);
+    memcpy(&top_p, p + r * 8 + 2, 4);
+    memcpy(&min_p, p + r * 8 + 3, 4);
+    TORCH_CHECK(t >= 0.0f && t <= 3.0e38f, "sample: row ", r,
+                " temperature must be finite and >= 0, got ", t);
+    TORCH_CHECK(top_p > 0.0f && top_p <= 1.0f, "sample: row ", r,
+                " top_p must be in (0, 1], got ", top_p);
+    TORCH_CHECK(min_p >= 0.0f && min_p <= 1.0f, "sample: row ", r,
+                " min_p must be in [0, 1], got ", min_p);
+  }
+}
+
+void sample(at::Tensor out, at::Tensor logits, at::Tensor params,
+            c10::optional<at::Tensor> u_in, c10::optional<at::Tensor> u_out) {
+  CHECK_GPU_DTYPE(out, at::kLong);
+  CHECK_GPU_BF16(logits);
+  CHECK_GPU_DTYPE(params, at::kInt);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0,
+              "logits must be [R, V] with R > 0 and V > 0");
+  const long R = logits.size(0);
+  TORCH_CHECK(logits.size(1) <= 0x7fffffffL, "V must fit an int32");
+  const int V = (int)logits.size(1);
+  TORCH_CHECK(out.numel() == R, "out must hold one index per row");
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == R && params.size(1) == 8,
+              "params must be [R, 8]");
+  TORCH_CHECK(out.device() == logits.device() &&
+                  params.device() == logits.device(),
+              "out and params must be on the logits' device");
+  const void* ui = nullptr;
+  void* uo = nullptr;
+  if (u_in.has_value()) {
+    CHECK_GPU_DTYPE(*u_in, at::kFloat);
+    TORCH_CHECK(u_in->numel() == R && u_in->device() == logits.device(),
+                "u must hold one value per row on the logits' device");
+    ui = u_in->data_ptr();
+  }
+  if (u_out.has_value()) {
+    CHECK_GPU_DTYPE(*u_out, at::kFloat);
+    TORCH_CHECK(u_out->numel() == R && u_out->device() == logits.device(),
+                "u_out must hold one value per row on the logits' device");
+    uo = u_out->data_ptr();
+  }
+  TORCH_CHECK(ps_sample(out.data_ptr(), uo, logits.data_ptr(),
+                        params.data_ptr(), ui, R, V, current_stream()) == 0,
+              "sample: bad shape");
+}
+
 void resolve_placeholders(at::Tensor tokens, at::Tensor prev_row,
                           at::Tensor prev_tokens) {
   CHECK_GPU_DTYPE(tokens, at::kLong);
@@ -1133,6 +1195,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reshape_and_cache", &reshape_and_cache,
         "Append K/V for new tokens into the paged cache");
   m.def("greedy_sample", &greedy_sample, "Per-row argmax over vocab");
+  m.def("sample", &sample,
+        "Per-row temperature / top-k / min-p / top-p sampling (csrc/sample.hip)",
+        py::arg("out"), py::arg("logits"), py::arg("params"),
+        py::arg("u_in") = py::none(), py::arg("u_out") = py::none());
+  m.def("sample_check", &sample_check,
+        "Validate a host tensor of sampling records");
   m.def("resolve_placeholders", &resolve_placeholders,
         "tokens[i] = prev_tokens[prev_row[i]] where prev_row[i] >= 0");
   m.def("pack_step_inputs", &pack_step_inputs,

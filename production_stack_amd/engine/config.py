@@ -408,6 +408,14 @@ class EngineConfig:
     # experts, for steps with T*top_k <= 1024;
     # routing stays on the device, decode hipGraphs are captured)
     moe_backend: str = "loop"
+    # stochastic sampling: "torch" (temperature rows through torch ops and
+    # a CPU multinomial; such steps leave the async-scheduling path) or
+    # "native" (csrc/sample.hip: temperature, top-k, min-p, top-p and the
+    # draw on the device, one launch per step, stochastic rows stay on the
+    # async path). "native" keeps whole tie classes at the top-p boundary
+    # and draws from a Philox stream of its own, so it does not reproduce
+    # "torch" token for token; temperature-0 rows are identical.
+    sampler: str = "torch"
     # draft-model speculative decoding (engine/draft.py): architecture
     # name of the (smaller, same-vocab) proposer; None = n-gram drafts
     speculative_model: Optional[str] = None

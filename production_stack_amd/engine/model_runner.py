@@ -112,6 +112,16 @@ class ModelRunner:
             )
         for layer in self.model.layers:
             layer.moe_backend = config.moe_backend
+        if config.sampler not in ("torch", "native"):
+            raise ValueError(
+                f"unknown sampler {config.sampler!r}; "
+                "expected 'torch' or 'native'"
+            )
+        # sampler == "native": draws made so far on the unseeded stream
+        # (Philox counter; seeded rows count their own output tokens)
+        self._native_draws = 1 << 32
+        # steps that left execute_async with a handle
+        self.async_steps = 0
         self._generator = torch.Generator(device="cpu").manual_seed(
             config.seed + 12345
         )
@@ -844,7 +854,9 @@ class ModelRunner:
         device-side greedy sampling WITHOUT any host sync; returns a
         handle the engine finalizes on the next step (one-step-lagged
         pipeline), or None when the step needs the sync path (non-greedy
-        sampling, speculative chunks, logprobs, TP/PP, no graphs).
+        sampling under sampler="torch", speculative chunks, logprobs, TP/PP,
+        no graphs). Under sampler="native" stochastic rows are sampled on
+        the device by ops.sample and stay on this path.
 
         Decode rows whose input token is still the -1 placeholder gather
         it on-device from the previous step's sampled tensor."""
@@ -855,9 +867,12 @@ class ModelRunner:
                 s.seq.lora_name for s in out.scheduled)
         ):
             return None
+        native_sampler = self.config.sampler == "native"
         for ss in out.scheduled:
             p = ss.seq.params
-            if not p.greedy or p.logprobs is not None or p.needs_penalties:
+            if not (p.greedy or native_sampler):
+                return None
+            if p.logprobs is not None or p.needs_penalties:
                 return None
             if getattr(p, "response_format", None):
                 return None  # guided masks need last step's token on host
@@ -938,11 +953,17 @@ class ModelRunner:
         sample_seqs = list(seqs_d) + list(seqs_p)
         if not sample_seqs:
             return None
+        # all-greedy steps keep the argmax kernel; one stochastic row sends
+        # the step's rows, greedy ones included, through ops.sample
+        stochastic = any(not s.params.greedy for s in sample_seqs)
         parts = []
-        if logits_d is not None and len(seqs_d):
-            parts.append(ops.greedy_sample(logits_d))
-        if logits_p is not None and len(seqs_p):
-            parts.append(ops.greedy_sample(logits_p))
+        for lg, sq in ((logits_d, seqs_d), (logits_p, seqs_p)):
+            if lg is None or not len(sq):
+                continue
+            if stochastic:
+                parts.append(ops.sample(lg, self._sample_records(sq)))
+            else:
+                parts.append(ops.greedy_sample(lg))
         sampled_dev = parts[0] if len(parts) == 1 else torch.cat(parts)
         # async D2H into pinned staging; two buffers alternate so the
         # in-flight previous step's values survive until its finalize
@@ -963,6 +984,7 @@ class ModelRunner:
         self._prev_rows = {
             seq.request_id: i for i, seq in enumerate(sample_seqs)
         }
+        self.async_steps += 1
         return {
             "out": out,
             "sample_seqs": sample_seqs,
@@ -1071,7 +1093,7 @@ class ModelRunner:
             logits = self._apply_penalties(logits, seqs)
         if any(getattr(p, "response_format", None) for p in params):
             logits = self._apply_guided(logits, seqs)
-        sampled = self.sample_params(logits, params)
+        sampled = self.sample_params(logits, params, seqs)
         want_lp = [i for i, p in enumerate(params)
                    if p.logprobs is not None]
         if want_lp:
@@ -1177,12 +1199,49 @@ class ModelRunner:
                         row[t] = float("-inf")
         return logits
 
+    def _sample_records(self, seqs: List, params: Optional[List] = None):
+        """ops.sample's record tensor for these rows. The random stream is
+        stateless per draw: a row with SamplingParams.seed uses key = seed
+        and counter = its output tokens so far (placeholders count, so sync
+        and async steps agree); any other row uses key = config.seed + 12345
+        and the runner's running draw count, which starts at 2^32. A row
+        given without its sequence draws from the unseeded stream."""
+        if params is None:
+            params = [s.params for s in seqs]
+        keys, ctrs = [], []
+        for i, p in enumerate(params):
+            seq = seqs[i] if seqs is not None else None
+            if p.seed is not None and seq is not None:
+                keys.append(int(p.seed))
+                ctrs.append(len(seq.output_token_ids))
+            else:
+                keys.append(self.config.seed + 12345)
+                ctrs.append(self._native_draws)
+                self._native_draws += 1
+        return ops.sample_pack(
+            [p.temperature for p in params],
+            [p.top_k for p in params],
+            [p.top_p for p in params],
+            [getattr(p, "min_p", 0.0) for p in params],
+            keys, ctrs,
+        )
+
     def sample_params(
-        self, logits: torch.Tensor, params: List
+        self, logits: torch.Tensor, params: List,
+        seqs: Optional[List] = None,
     ) -> torch.Tensor:
-        """Batched sampling: greedy rows via the HIP argmax kernel, the rest
-        through grouped tensor ops (temperature -> per-group top-k ->
-        sorted-cumsum top-p -> multinomial), one batch per distinct top_k."""
+        """Batched sampling. sampler="native": one ops.sample launch over
+        all rows, greedy ones included, whenever the logits are bf16 (rows
+        that penalties or guided decoding turned to fp32 take the torch path
+        for that step). sampler="torch": greedy rows via the HIP argmax
+        kernel, the rest through grouped tensor ops (temperature ->
+        per-group top-k -> sorted-cumsum top-p -> multinomial), one batch
+        per distinct top_k."""
+        if (self.config.sampler == "native"
+                and ops.sample_supported(logits) and len(params)):
+            return ops.sample(
+                logits, self._sample_records(seqs, params)
+            ).cpu()
         greedy_mask = torch.tensor([p.greedy for p in params])
         result = torch.empty(len(params), dtype=torch.long)
         if bool(greedy_mask.all()):

@@ -1255,6 +1255,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
                     choices=["loop", "fused"],
                     help="fused = grouped MoE expert kernels + decode "
                          "hipGraphs for Mixtral-family models")
+    ap.add_argument("--sampler", default="torch",
+                    choices=["torch", "native"],
+                    help="native = hand-written HIP sampler (temperature, "
+                         "top-k, min-p, top-p and the draw on the device); "
+                         "stochastic requests stay on the async-scheduling "
+                         "path. Its random stream and its top-p tie rule "
+                         "differ from torch's")
     ap.add_argument("--no-unified-mixed-steps", dest="unified_mixed_steps",
                     action="store_false", default=True)
     ap.add_argument("--async-scheduling", action="store_true",
@@ -1327,6 +1334,7 @@ def main() -> None:
         fp8_gemm=args.fp8_gemm,
         int4_gemm=args.int4_gemm,
         moe_backend=args.moe_backend,
+        sampler=args.sampler,
         enable_lora=args.enable_lora,
         max_loras=args.max_loras,
         max_lora_rank=args.max_lora_rank,

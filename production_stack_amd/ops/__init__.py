@@ -9,6 +9,7 @@ the engine and its tests work in GPU-less CI.
 from __future__ import annotations
 
 import os
+import struct
 from typing import Optional
 
 import torch
@@ -287,6 +288,72 @@ def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
         _C.greedy_sample(out, logits)
         return out
     return reference.greedy_sample(logits)
+
+
+def sample_supported(logits: torch.Tensor) -> bool:
+    """Whether ops.sample takes these logits: bf16 [R, V], contiguous."""
+    return (
+        logits.dtype == torch.bfloat16 and logits.dim() == 2
+        and logits.is_contiguous()
+    )
+
+
+def sample_pack(
+    temperature, top_k, top_p, min_p, key, counter
+) -> torch.Tensor:
+    """The [R, 8] int32 record tensor ops.sample reads, from per-row lists:
+    32 bytes a row (fp32 temperature, int32 top_k, fp32 top_p, fp32 min_p,
+    uint64 Philox key, uint64 Philox counter). Pinned when there is a GPU,
+    so ops.sample uploads it with one asynchronous copy."""
+    buf = bytearray()
+    for t, k, p, m, ky, c in zip(temperature, top_k, top_p, min_p, key,
+                                 counter):
+        k = int(k)
+        buf += struct.pack(
+            "<fiffQQ", t, min(k, 0x7FFFFFFF) if k > 0 else -1, p, m,
+            int(ky) & 0xFFFFFFFFFFFFFFFF, int(c) & 0xFFFFFFFFFFFFFFFF,
+        )
+    rec = torch.empty(
+        (len(buf) // 32, 8), dtype=torch.int32,
+        pin_memory=torch.cuda.is_available(),
+    )
+    if len(buf):
+        rec.copy_(torch.frombuffer(buf, dtype=torch.int32).view(-1, 8))
+    return rec
+
+
+def sample(
+    logits: torch.Tensor, params: torch.Tensor,
+    u: Optional[torch.Tensor] = None, return_u: bool = False,
+):
+    """One token id per logits row (int64 [R] on the logits' device) under the
+    row's record in `params` (sample_pack): argmax where temperature == 0,
+    else temperature, top-k, min-p, top-p and one draw with the row's Philox
+    uniform, or with u[r] where `u` (fp32 [R]) is given. return_u also
+    returns the uniforms used. csrc/sample.hip states the contract."""
+    if not sample_supported(logits):
+        raise ValueError(
+            "ops.sample takes contiguous bf16 [R, V] logits, got "
+            f"{logits.dtype} {tuple(logits.shape)}"
+        )
+    R, V = logits.shape
+    if R < 1 or V < 1:
+        raise ValueError(f"ops.sample needs R >= 1 and V >= 1, got {R}x{V}")
+    if tuple(params.shape) != (R, 8) or params.dtype != torch.int32:
+        raise ValueError("ops.sample params must be int32 [R, 8]")
+    if not logits.is_cuda:
+        return reference.sample(logits, params, u, return_u)
+    _require_ext()
+    if not params.is_cuda:
+        _C.sample_check(params)
+        params = params.to(logits.device, non_blocking=True)
+    out = torch.empty(R, dtype=torch.long, device=logits.device)
+    u_out = (
+        torch.empty(R, dtype=torch.float32, device=logits.device)
+        if return_u else None
+    )
+    _C.sample(out, logits, params, u, u_out)
+    return (out, u_out) if return_u else out
 
 
 def resolve_placeholders(

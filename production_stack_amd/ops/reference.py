@@ -12,6 +12,9 @@ They intentionally mirror the kernel semantics exactly (paged cache layout
 
 from __future__ import annotations
 
+import math
+import struct
+
 import torch
 
 
@@ -171,6 +174,76 @@ def paged_attn_prefill(
 
 def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
     return logits.float().argmax(dim=-1)
+
+
+_M32 = 0xFFFFFFFF
+
+
+def philox_uniform(key: int, counter: int) -> float:
+    """The sampler's uniform: Philox-4x32-10 on counter {lo, hi, 0, 0} and
+    key {lo, hi}; (word 0 >> 8) * 2^-24, in [0, 1) and exact in fp32."""
+    c = [counter & _M32, (counter >> 32) & _M32, 0, 0]
+    k0, k1 = key & _M32, (key >> 32) & _M32
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & _M32,
+             (p0 >> 32) ^ c[3] ^ k1, p0 & _M32]
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return (c[0] >> 8) * 2.0 ** -24
+
+
+def sample_unpack(params: torch.Tensor) -> list:
+    """[(temperature, top_k, top_p, min_p, key, counter)] of an [R, 8] int32
+    record tensor (ops.sample_pack), with the range checks ops.sample makes."""
+    raw = params.detach().cpu().contiguous().numpy().tobytes()
+    rows = list(struct.iter_unpack("<fiffQQ", raw))
+    for r, (t, _, top_p, min_p, _, _) in enumerate(rows):
+        if not 0.0 <= t <= 3.0e38:
+            raise ValueError(f"sample: row {r} temperature must be finite "
+                             f"and >= 0, got {t}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(
+                f"sample: row {r} top_p must be in (0, 1], got {top_p}")
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(
+                f"sample: row {r} min_p must be in [0, 1], got {min_p}")
+    return rows
+
+
+def sample(logits: torch.Tensor, params: torch.Tensor, u=None,
+           return_u: bool = False):
+    """csrc/sample.hip's contract a row at a time: top-k, min-p and top-p as
+    thresholds on the logit value (ties stay together), then the first kept
+    token, in token-id order, whose running mass exceeds u * Z."""
+    R, V = logits.shape
+    out = torch.empty(R, dtype=torch.long)
+    used = torch.empty(R, dtype=torch.float32)
+    for r, (t, top_k, top_p, min_p, key, ctr) in enumerate(
+            sample_unpack(params)):
+        used[r] = float(u[r]) if u is not None else philox_uniform(key, ctr)
+        x = logits[r].float()
+        if t == 0.0:
+            out[r] = greedy_sample(x)
+            continue
+        keep = ~torch.isnan(x)
+        if 0 < top_k < V:
+            keep &= x >= torch.topk(x, top_k).values[-1]
+        s = x / t
+        d = s - s.max()
+        if min_p > 0.0:
+            keep &= d >= math.log(min_p)
+        p = torch.exp(d) * keep
+        if top_p < 1.0:
+            sp = torch.sort(p[keep], descending=True).values.double()
+            before = torch.cumsum(sp, 0) - sp
+            b = int((before < top_p * sp.sum()).nonzero()[-1])
+            keep &= p >= sp[b].float()
+            p = p * keep
+        cdf = torch.cumsum(p.double(), 0)
+        i = int(torch.searchsorted(cdf, used[r].double() * cdf[-1],
+                                   right=True))
+        out[r] = i if i < V else int(keep.nonzero()[-1])
+    return (out, used) if return_u else out
 
 
 def resolve_placeholders(

@@ -46,6 +46,7 @@ ext = CUDAExtension(
         "csrc/moe_fused.hip",
         "csrc/moe_fused_w4.hip",
         "csrc/step_inputs.hip",
+        "csrc/sample.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
