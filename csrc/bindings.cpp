@@ -76,6 +76,10 @@ void ps_greedy_sample(void* out, const void* logits, long R, int V,
 // non-zero, launching nothing, when R < 1 or V < 1
 int ps_sample(void* out, void* u_out, const void* logits, const void* params,
               const void* u_in, long R, int V, hipStream_t stream);
+// non-zero, launching nothing, when M < 1, R < 1, V < 1 or N outside [0, 20]
+int ps_logprobs(void* lp, void* top_ids, void* top_lp, const void* logits,
+                const void* token_ids, const void* rows, long M, long R,
+                int V, int N, hipStream_t stream);
 void ps_kv_quant(void* out, void* scales, const void* in, long rows, int hd,
                  hipStream_t stream);
 void ps_kv_dequant(void* out, const void* in, const void* scales, long rows,
@@ -1066,6 +1070,50 @@ void sample(at::Tensor out, at::Tensor logits, at::Tensor params,
               "sample: bad shape");
 }
 
+// lp[m], top_ids[m, :], top_lp[m, :] for logits row rows[m] (row m without
+// rows) and the token token_ids[rows[m]]: csrc/logprobs.hip.
+void logprobs(at::Tensor lp, at::Tensor top_ids, at::Tensor top_lp,
+              at::Tensor logits, at::Tensor token_ids,
+              c10::optional<at::Tensor> rows, long top_n) {
+  CHECK_GPU_BF16(logits);
+  CHECK_GPU_DTYPE(token_ids, at::kLong);
+  CHECK_GPU_DTYPE(lp, at::kFloat);
+  CHECK_GPU_DTYPE(top_ids, at::kInt);
+  CHECK_GPU_DTYPE(top_lp, at::kFloat);
+  TORCH_CHECK(top_n >= 0 && top_n <= 20, "logprobs: top_n must be in [0, 20], "
+              "got ", top_n);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0,
+              "logits must be [R, V] with R > 0 and V > 0");
+  const long R = logits.size(0);
+  TORCH_CHECK(logits.size(1) <= 0x7fffffffL, "V must fit an int32");
+  const int V = (int)logits.size(1);
+  TORCH_CHECK(token_ids.dim() == 1 && token_ids.numel() == R,
+              "token_ids must hold one id per logits row");
+  long M = R;
+  const void* rp = nullptr;
+  if (rows.has_value()) {
+    CHECK_GPU_DTYPE(*rows, at::kInt);
+    TORCH_CHECK(rows->dim() == 1 && rows->device() == logits.device(),
+                "rows must be 1-D on the logits' device");
+    M = rows->numel();
+    rp = rows->data_ptr();
+  }
+  TORCH_CHECK(lp.numel() == M, "lp must hold one value per requested row");
+  TORCH_CHECK(top_ids.numel() == M * top_n && top_lp.numel() == M * top_n,
+              "top_ids and top_lp must be [M, top_n]");
+  TORCH_CHECK(token_ids.device() == logits.device() &&
+                  lp.device() == logits.device() &&
+                  top_ids.device() == logits.device() &&
+                  top_lp.device() == logits.device(),
+              "token_ids and the outputs must be on the logits' device");
+  if (M == 0) return;
+  TORCH_CHECK(ps_logprobs(lp.data_ptr(), top_ids.data_ptr(),
+                          top_lp.data_ptr(), logits.data_ptr(),
+                          token_ids.data_ptr(), rp, M, R, V, (int)top_n,
+                          current_stream()) == 0,
+              "logprobs: bad shape");
+}
+
 void resolve_placeholders(at::Tensor tokens, at::Tensor prev_row,
                           at::Tensor prev_tokens) {
   CHECK_GPU_DTYPE(tokens, at::kLong);
@@ -1201,6 +1249,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("u_in") = py::none(), py::arg("u_out") = py::none());
   m.def("sample_check", &sample_check,
         "Validate a host tensor of sampling records");
+  m.def("logprobs", &logprobs,
+        "Per-row token logprob and top-N alternatives (csrc/logprobs.hip)",
+        py::arg("lp"), py::arg("top_ids"), py::arg("top_lp"),
+        py::arg("logits"), py::arg("token_ids"), py::arg("rows") = py::none(),
+        py::arg("top_n") = 0);
   m.def("resolve_placeholders", &resolve_placeholders,
         "tokens[i] = prev_tokens[prev_row[i]] where prev_row[i] >= 0");
   m.def("pack_step_inputs", &pack_step_inputs,

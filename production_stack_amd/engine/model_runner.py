@@ -141,6 +141,8 @@ class ModelRunner:
         self._prev_rows: Dict[str, int] = {}
         self._async_host = [None, None]
         self._async_host_i = 0
+        # pinned (lp, top_ids, top_lp) staging, alternating as the tokens' does
+        self._async_lp_host = [None, None]
         # native step-input path (prepare_native): two pinned staging
         # buffers + device arenas used alternately, each with the event of
         # its last upload. PS_NATIVE_PREPARE=0 forces prepare() for A/B.
@@ -854,9 +856,11 @@ class ModelRunner:
         device-side greedy sampling WITHOUT any host sync; returns a
         handle the engine finalizes on the next step (one-step-lagged
         pipeline), or None when the step needs the sync path (non-greedy
-        sampling under sampler="torch", speculative chunks, logprobs, TP/PP,
-        no graphs). Under sampler="native" stochastic rows are sampled on
-        the device by ops.sample and stay on this path.
+        sampling or logprobs under sampler="torch", speculative chunks,
+        prompt_logprobs, TP/PP, no graphs). Under sampler="native" stochastic
+        rows are sampled on the device by ops.sample, logprobs come from
+        ops.logprobs on the sampled device tensor, and both stay on this
+        path.
 
         Decode rows whose input token is still the -1 placeholder gather
         it on-device from the previous step's sampled tensor."""
@@ -872,8 +876,10 @@ class ModelRunner:
             p = ss.seq.params
             if not (p.greedy or native_sampler):
                 return None
-            if p.logprobs is not None or p.needs_penalties:
+            if p.needs_penalties:
                 return None
+            if p.logprobs is not None and not native_sampler:
+                return None  # the native sampler has ops.logprobs
             if getattr(p, "response_format", None):
                 return None  # guided masks need last step's token on host
             if getattr(p, "prompt_logprobs", None) is not None:
@@ -956,7 +962,12 @@ class ModelRunner:
         # all-greedy steps keep the argmax kernel; one stochastic row sends
         # the step's rows, greedy ones included, through ops.sample
         stochastic = any(not s.params.greedy for s in sample_seqs)
-        parts = []
+        lp_seqs = [s for s in sample_seqs if s.params.logprobs is not None]
+        lp_n = min(
+            max((int(s.params.logprobs or 0) for s in lp_seqs), default=0),
+            ops.LOGPROBS_MAX_TOP,
+        )
+        parts, lp_parts = [], []
         for lg, sq in ((logits_d, seqs_d), (logits_p, seqs_p)):
             if lg is None or not len(sq):
                 continue
@@ -964,6 +975,13 @@ class ModelRunner:
                 parts.append(ops.sample(lg, self._sample_records(sq)))
             else:
                 parts.append(ops.greedy_sample(lg))
+            ps = [s.params for s in sq]
+            if any(p.logprobs is not None for p in ps):
+                # native sampler only (checked above): the logprobs kernel
+                # reads the device token tensor the sampler just wrote
+                lp_parts.append(
+                    self._launch_logprobs(lg, parts[-1], ps, lp_n)
+                )
         sampled_dev = parts[0] if len(parts) == 1 else torch.cat(parts)
         # async D2H into pinned staging; two buffers alternate so the
         # in-flight previous step's values survive until its finalize
@@ -976,6 +994,9 @@ class ModelRunner:
             )
             self._async_host[self._async_host_i] = host
         host[: sampled_dev.numel()].copy_(sampled_dev, non_blocking=True)
+        lp_host = None
+        if lp_parts:
+            lp_host = self._stage_logprobs(lp_parts, len(lp_seqs), lp_n)
         ev = None
         if self.device.type == "cuda":
             ev = torch.cuda.Event()
@@ -991,12 +1012,41 @@ class ModelRunner:
             "host": host,
             "n": sampled_dev.numel(),
             "event": ev,
+            "lp_seqs": lp_seqs,
+            "lp_host": lp_host,
         }
 
+    def _stage_logprobs(self, lp_parts, m: int, n: int):
+        """Copy ops.logprobs' outputs, non-blocking, into this step's pinned
+        staging (the buffer pair alternates with the token staging) and
+        return host views (lp [m], top_ids [m, n], top_lp [m, n])."""
+        stage = self._async_lp_host[self._async_host_i]
+        if stage is None or stage[0].numel() < m:
+            cap = max(m, 64)
+            pin = self.device.type == "cuda"
+            stage = (
+                torch.empty(cap, dtype=torch.float32, pin_memory=pin),
+                torch.empty(cap * ops.LOGPROBS_MAX_TOP, dtype=torch.int32,
+                            pin_memory=pin),
+                torch.empty(cap * ops.LOGPROBS_MAX_TOP, dtype=torch.float32,
+                            pin_memory=pin),
+            )
+            self._async_lp_host[self._async_host_i] = stage
+        views = (stage[0][:m], stage[1][: m * n].view(m, n),
+                 stage[2][: m * n].view(m, n))
+        for j, view in enumerate(views):
+            src = [part[j] for part in lp_parts]
+            view.copy_(src[0] if len(src) == 1 else torch.cat(src),
+                       non_blocking=True)
+        return views
+
     def finalize_async(self, handle) -> Dict[str, int]:
-        """Wait for the handle's D2H and return request_id -> token."""
+        """Wait for the handle's D2H and return request_id -> token; fills
+        last_logprobs / last_top_logprobs of the rows that asked."""
         if handle["event"] is not None:
             handle["event"].synchronize()
+        if handle["lp_host"] is not None:
+            self._store_logprobs(handle["lp_seqs"], *handle["lp_host"])
         vals = handle["host"][: handle["n"]].tolist()
         return {
             seq.request_id: int(t)
@@ -1024,17 +1074,21 @@ class ModelRunner:
                     idx_rows = torch.arange(
                         row, row + count, device=hidden.device
                     )
-                    lg = torch.log_softmax(
-                        self.model.compute_logits(
-                            hidden.index_select(0, idx_rows)
-                        ).float(),
-                        dim=-1,
+                    lg = self.model.compute_logits(
+                        hidden.index_select(0, idx_rows)
                     )
                     ids = torch.tensor(
                         seq.prompt_token_ids[start + 1:start + 1 + count],
                         dtype=torch.long, device=lg.device,
                     )
-                    vals = lg.gather(1, ids.unsqueeze(1)).squeeze(1)
+                    if (self.config.sampler == "native"
+                            and ops.logprobs_supported(lg)):
+                        # one workgroup per row, two reads of it: no fp32
+                        # [count, V] tensor
+                        vals = ops.logprobs(lg, ids, 0)[0]
+                    else:
+                        lg = torch.log_softmax(lg.float(), dim=-1)
+                        vals = lg.gather(1, ids.unsqueeze(1)).squeeze(1)
                     acc = self.prompt_logprobs.setdefault(
                         seq.request_id, [None]
                     )
@@ -1093,9 +1147,21 @@ class ModelRunner:
             logits = self._apply_penalties(logits, seqs)
         if any(getattr(p, "response_format", None) for p in params):
             logits = self._apply_guided(logits, seqs)
-        sampled = self.sample_params(logits, params, seqs)
         want_lp = [i for i, p in enumerate(params)
                    if p.logprobs is not None]
+        if (want_lp and self.config.sampler == "native"
+                and ops.logprobs_supported(logits)):
+            # one ops.logprobs launch on the device token tensor, three
+            # small copies back: no fp32 [rows, V] tensor, no per-row topk
+            sampled_dev = ops.sample(
+                logits, self._sample_records(seqs, params)
+            )
+            got = self._launch_logprobs(logits, sampled_dev, params)
+            self._store_logprobs(
+                [seqs[i] for i in want_lp], *(t.cpu() for t in got)
+            )
+            return sampled_dev.cpu()
+        sampled = self.sample_params(logits, params, seqs)
         if want_lp:
             idx = torch.tensor(want_lp, dtype=torch.long,
                                device=logits.device)
@@ -1115,6 +1181,39 @@ class ModelRunner:
                         (float(v) for v in tv.cpu()),
                     ))
         return sampled
+
+    def _launch_logprobs(self, logits, tokens_dev, params, top_n=None):
+        """ops.logprobs over the rows whose params ask for logprobs, with one
+        launch-wide N (the largest request, capped at 20, unless given).
+        Returns the three device outputs, entry m for the m-th such row."""
+        want = [i for i, p in enumerate(params) if p.logprobs is not None]
+        if top_n is None:
+            top_n = min(
+                max(int(params[i].logprobs or 0) for i in want),
+                ops.LOGPROBS_MAX_TOP,
+            )
+        rows = None
+        if len(want) != len(params):
+            rows = torch.tensor(want, dtype=torch.int32).to(
+                logits.device, non_blocking=True
+            )
+        return ops.logprobs(logits, tokens_dev, top_n, rows)
+
+    def _store_logprobs(self, seqs, lp, top_ids, top_lp) -> None:
+        """Fill last_logprobs / last_top_logprobs from ops.logprobs' outputs
+        on the host; a row that asked for fewer alternatives than the launch
+        computed keeps its prefix."""
+        lp, top_ids, top_lp = lp.tolist(), top_ids.tolist(), top_lp.tolist()
+        for m, seq in enumerate(seqs):
+            if seq.finished:  # a lagged step past the sequence's end
+                continue
+            rid = seq.request_id
+            self.last_logprobs[rid] = lp[m]
+            k = min(int(seq.params.logprobs or 0), ops.LOGPROBS_MAX_TOP)
+            pairs = [(t, v) for t, v in zip(top_ids[m][:k], top_lp[m][:k])
+                     if t >= 0]
+            if pairs:
+                self.last_top_logprobs[rid] = pairs
 
     def _apply_guided(
         self, logits: torch.Tensor, seqs: List[Sequence]

@@ -356,6 +356,54 @@ def sample(
     return (out, u_out) if return_u else out
 
 
+LOGPROBS_MAX_TOP = 20  # the cap on alternatives per position
+
+
+def logprobs_supported(logits: torch.Tensor) -> bool:
+    """Whether ops.logprobs takes these logits: bf16 [R, V], contiguous."""
+    return sample_supported(logits)
+
+
+def logprobs(
+    logits: torch.Tensor, token_ids: torch.Tensor, top_n: int = 0,
+    rows: Optional[torch.Tensor] = None,
+):
+    """(lp fp32 [M], top_ids int32 [M, top_n], top_lp fp32 [M, top_n]) for
+    the logits rows `rows` (int32 [M]; every row when None): the logprob of
+    token_ids[row] (int64 [R], ids in [0, V)) and the top_n largest logits as
+    (id, logprob), descending, equal logits by ascending id, -1 / -inf past
+    V. One launch, no copy of the rows. csrc/logprobs.hip states the
+    contract."""
+    if not logprobs_supported(logits):
+        raise ValueError(
+            "ops.logprobs takes contiguous bf16 [R, V] logits, got "
+            f"{logits.dtype} {tuple(logits.shape)}"
+        )
+    R, V = logits.shape
+    if R < 1 or V < 1:
+        raise ValueError(f"ops.logprobs needs R >= 1 and V >= 1, got {R}x{V}")
+    top_n = int(top_n)
+    if not 0 <= top_n <= LOGPROBS_MAX_TOP:
+        raise ValueError(
+            f"ops.logprobs top_n must be in [0, {LOGPROBS_MAX_TOP}], "
+            f"got {top_n}"
+        )
+    if token_ids.dtype != torch.long or tuple(token_ids.shape) != (R,):
+        raise ValueError("ops.logprobs token_ids must be int64 [R]")
+    if rows is not None and (rows.dtype != torch.int32 or rows.dim() != 1):
+        raise ValueError("ops.logprobs rows must be int32 [M]")
+    if not logits.is_cuda:
+        return reference.logprobs(logits, token_ids, top_n, rows)
+    _require_ext()
+    M = R if rows is None else rows.numel()
+    dev = logits.device
+    lp = torch.empty(M, dtype=torch.float32, device=dev)
+    top_ids = torch.empty((M, top_n), dtype=torch.int32, device=dev)
+    top_lp = torch.empty((M, top_n), dtype=torch.float32, device=dev)
+    _C.logprobs(lp, top_ids, top_lp, logits, token_ids, rows, top_n)
+    return lp, top_ids, top_lp
+
+
 def resolve_placeholders(
     tokens: torch.Tensor, prev_row: torch.Tensor, prev_tokens: torch.Tensor
 ) -> torch.Tensor:

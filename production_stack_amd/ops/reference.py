@@ -246,6 +246,36 @@ def sample(logits: torch.Tensor, params: torch.Tensor, u=None,
     return (out, used) if return_u else out
 
 
+def logprobs(logits: torch.Tensor, token_ids: torch.Tensor, top_n: int = 0,
+             rows=None):
+    """csrc/logprobs.hip's contract: per requested row the logprob of its
+    token and the top_n largest logits as (id, logprob), descending, equal
+    logits by ascending id; NaN carries no mass, orders below -inf and reads
+    -inf; slots past V hold -1 and -inf."""
+    R, V = logits.shape
+    sel = torch.arange(R) if rows is None else rows.long()
+    x = logits.index_select(0, sel).double()
+    nan = torch.isnan(x)
+    x = x.masked_fill(nan, float("-inf"))
+    lp_all = (x - torch.logsumexp(x, dim=-1, keepdim=True)).float()
+    tok = token_ids.index_select(0, sel)
+    lp = lp_all.gather(1, tok.unsqueeze(1)).squeeze(1)
+    M = sel.numel()
+    top_ids = torch.full((M, top_n), -1, dtype=torch.int32)
+    top_lp = torch.full((M, top_n), float("-inf"), dtype=torch.float32)
+    n = min(top_n, V)
+    if n:
+        # a stable descending sort keeps equal logits in id order; -inf is
+        # lifted to a finite key so that NaN alone sorts last
+        order = torch.sort(
+            x.clamp(min=-1e300).masked_fill(nan, float("-inf")),
+            dim=-1, descending=True, stable=True,
+        ).indices[:, :n]
+        top_ids[:, :n] = order.int()
+        top_lp[:, :n] = lp_all.gather(1, order)
+    return lp, top_ids, top_lp
+
+
 def resolve_placeholders(
     tokens: torch.Tensor, prev_row: torch.Tensor, prev_tokens: torch.Tensor
 ) -> torch.Tensor:

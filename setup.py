@@ -47,6 +47,7 @@ ext = CUDAExtension(
         "csrc/moe_fused_w4.hip",
         "csrc/step_inputs.hip",
         "csrc/sample.hip",
+        "csrc/logprobs.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
