@@ -746,7 +746,7 @@ int ps_paged_attn_decode(void* out, void* ws_acc, void* ws_ml, const void* q,
       default: return -1;
     }
   }
-  if (head_dim == 64 && block_size == 16 && !kv_fp8) {
+  if (head_dim == 64 && block_size == 16) {
     switch (GQ) {
       case 1: PS_DISPATCH_DECODE(64, 1, 16); return 0;
       case 2: PS_DISPATCH_DECODE(64, 2, 16); return 0;

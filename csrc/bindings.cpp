@@ -54,6 +54,15 @@ int ps_paged_attn_prefill_mfma32(void* out, void* ws_o, void* ws_ml,
                                  float scale, int KH, int GQ, int head_dim,
                                  long q_stride, int kv_fp8, int window,
                                  hipStream_t stream);
+int ps_paged_attn_prefill_mfma64(void* out, void* ws_o, void* ws_ml,
+                                 long q_tokens, const void* q,
+                                 const void* k_cache, const void* v_cache,
+                                 const void* block_tables,
+                                 const void* tile_info, int num_tiles,
+                                 int num_q_heads, int max_blocks,
+                                 float scale, int KH, int GQ, int head_dim,
+                                 long q_stride, int kv_fp8, int window,
+                                 hipStream_t stream);
 int ps_paged_attn_prefill_mfma(void* out, const void* q, const void* k_cache,
                                const void* v_cache, const void* block_tables,
                                const void* tile_info, int num_tiles,
@@ -411,7 +420,11 @@ void paged_attn_prefill_mfma(at::Tensor out, at::Tensor q,
       ws_o_p = ws_o.data_ptr();
       ws_ml_p = ws_ml.data_ptr();
     }
-    rc = ps_paged_attn_prefill_mfma32(
+    // head_dim 64 has a kernel of its own (csrc/prefill_mfma64.hip) with
+    // v5's tiles, split rule and workspace layout
+    auto launch = HD == 64 ? ps_paged_attn_prefill_mfma64
+                           : ps_paged_attn_prefill_mfma32;
+    rc = launch(
         out.data_ptr(), ws_o_p, ws_ml_p, T, q.data_ptr(),
         k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
         tile_info.data_ptr(), NT, QH, (int)block_tables.size(1),
@@ -1233,7 +1246,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lora_bgmv", &lora_bgmv,
         "batched-grouped LoRA matvec (per-token adapter slots)");
   m.def("paged_attn_prefill_mfma", &paged_attn_prefill_mfma,
-        "Paged attention, chunked prefill via MFMA tiles (head_dim 128)",
+        "Paged attention, chunked prefill via MFMA tiles (head_dim 128; "
+        "variant 5 also head_dim 64)",
         pybind11::arg("out"), pybind11::arg("q"), pybind11::arg("k_cache"),
         pybind11::arg("v_cache"), pybind11::arg("block_tables"),
         pybind11::arg("tile_info"), pybind11::arg("scale"),

@@ -275,7 +275,7 @@ class LlamaLayer(nn.Module):
             qh.is_cuda
             and 0 < tp < T
             and meta.num_decode_seqs > 0
-            and self.head_dim == 128
+            and ops.prefill_mfma_supported(self.head_dim)
             and meta.prefill_tiles is not None
         ):
             buf = torch.empty(
@@ -285,7 +285,7 @@ class LlamaLayer(nn.Module):
         if tp > 0:
             if (
                 qh.is_cuda
-                and self.head_dim == 128
+                and ops.prefill_mfma_supported(self.head_dim)
                 and meta.prefill_tiles is not None
             ):
                 outs.append(

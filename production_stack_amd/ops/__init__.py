@@ -239,6 +239,13 @@ def prefill_tile_rows(num_q_heads: int, num_kv_heads: int) -> int:
     return 32 * (8 // gqw)
 
 
+def prefill_mfma_supported(head_dim: int) -> bool:
+    """Whether paged_attn_prefill_mfma serves this head_dim with the active
+    variant: 128 always; 64 only by variant 5 (csrc/prefill_mfma64.hip), so
+    PS_PREFILL_VARIANT=3 sends a head_dim-64 model to the VALU kernel."""
+    return head_dim == 128 or (head_dim == 64 and PREFILL_VARIANT == 5)
+
+
 def paged_attn_prefill_mfma(
     q: torch.Tensor,
     k_cache: torch.Tensor,
@@ -250,7 +257,8 @@ def paged_attn_prefill_mfma(
     variant: int = None,
     out: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
-    """MFMA-tiled chunked prefill (GPU, head_dim 128 only). tile_info rows
+    """MFMA-tiled chunked prefill (GPU; head_dim 128, and with variant 5
+    head_dim 64, see prefill_mfma_supported). tile_info rows
     must be built with n_rows <= prefill_tile_rows() for the active
     variant. `out` (contiguous, q's shape and dtype) receives the result.
 

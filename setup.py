@@ -35,6 +35,7 @@ ext = CUDAExtension(
         "csrc/attention.hip",
         "csrc/prefill_mfma.hip",
         "csrc/prefill_mfma32.hip",
+        "csrc/prefill_mfma64.hip",
         "csrc/skinny_gemm.hip",
         "csrc/skinny_gemm_fp8.hip",
         "csrc/skinny_gemm_w4.hip",
